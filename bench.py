@@ -2,7 +2,7 @@
 """Benchmark of the BASELINE metric: training images/s of cfg_kitti_tripleD (ResNet50 depth +
 feature nets, ResNet18 pose net, 192x640, 12 images per GPU) on 1..8 MI355X.
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,8 +10,15 @@ A step = forward (depth/pose/auto-encoder nets under bf16 autocast, channels_las
 path in the hand-written fp32 HIP kernels) + backward + gradient sync (bucketed RCCL all-reduce
 overlapped with backward when N > 1) + grad-clip + Adam, on synthetic frame triplets already
 resident in HBM.  Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for the field
-definitions (roofline = the dominant hand-written kernel timed live with HIP events;
-cpu_baseline = the same training step with the CPU oracle loss path on the host cores).
+definitions.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step,
+config).  ``--dump-outputs DIR`` also writes what the last timed step handed back (total loss, loss
+entries, the model's floating-point outputs) as DIR/<name>.npy; that step then starts from the initial
+parameters, so that the arrays are the same in every run.  Everything that takes runs of its
+own is behind ``--full``: runner_entry = the same iteration through train.py's path; roofline = the
+dominant hand-written kernel timed live with HIP events, before and after the run, and the loss path
+as one graph; cpu_baseline = the same training step with the CPU oracle loss path on the host cores.
 """
 import argparse
 import json
@@ -89,8 +96,14 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--config", default=os.path.join(ROOT, "config", "cfg_kitti_tripleD.py"))
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the runner entry (--entry), the kernel and loss-path "
+                        "rooflines and the CPU baseline (each with its own --no-... switch)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last one returned (loss, loss entries, floating-point model outputs) "
+                        "as DIR/<name>.npy, float32, at most 60 MB in all (larger arrays: a fixed seeded sample of their elements)")
     p.add_argument("--no-graph", action="store_true", help="do not capture the step in a HIP graph")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--prune-extractor-tail", action="store_true",
                    help="skip the ResNet tails whose output the reference discards (net.py:221); NOT the headline configuration")
     p.add_argument("--h2d", nargs="?", const="float32", default=None, choices=["float32", "uint8"],
@@ -103,7 +116,7 @@ def parse():
     p.add_argument("--frames", default="coherent", choices=["coherent", "iid"],
                    help="coherent: the three frames are shifted crops of one canvas (like driving data; the headline input); "
                         "iid: independent uniform noise per frame (the adversarial case of SURVEY.md section 8d)")
-    p.add_argument("--no-roofline", action="store_true", help="skip the isolated kernel timing (profiling runs)")
+    p.add_argument("--no-roofline", action="store_true", help="with --full: skip the isolated kernel timing (profiling runs)")
     p.add_argument("--fp8", action="store_true", help="forward GEMM of the eligible 1x1 convolutions on the fp8 MFMA path "
                                                       "(BASELINE config 5; off by default: measured slower at these sizes, DESIGN.md)")
     p.add_argument("--allow-fallbacks", action="store_true",
@@ -115,12 +128,30 @@ def parse():
                         "layer and direction) or local statistics; default: what the config says (cfg_kitti_tripleD: syncbn=True)")
     p.add_argument("--entry", default="both", choices=["step", "runner", "both"],
                    help="step: tripled_amd.step.TrainStep replayed by this script (`value`); runner: the same iteration through "
-                        "train_mono / the mmcv Runner, i.e. what train.py executes (`runner_entry`); both (default)")
+                        "train_mono / the mmcv Runner, i.e. what train.py executes (`runner_entry`); both (default).  The runner "
+                        "entry is a run of its own and needs --full")
     p.add_argument("--grad-sync", default="auto", choices=["auto", "overlap-graph", "two-graph", "eager"],
                    help="N > 1 gradient exchange (auto: overlap-graph, falling back to two-graph, then eager)")
-    p.add_argument("--miopen-find", default="config", choices=["config", "on", "off"],
-                   help="torch.backends.cudnn.benchmark = MIOpen find mode; default: the config's cudnn_benchmark")
-    return p.parse_args()
+    p.add_argument("--miopen-find", default="auto", choices=["auto", "config", "on", "off"],
+                   help="torch.backends.cudnn.benchmark = MIOpen find mode.  on: MIOpen searches its solvers in the first step, again in "
+                        "every process (about a minute for cfg_kitti_tripleD, nearly three while its kernel cache is empty); off: "
+                        "immediate mode, which takes the best solver of MIOpen's user find-db where one is recorded; config: the config's "
+                        "cudnn_benchmark, as train.py sets it; auto (default): off for the default config when build() has left a find-db "
+                        "of such a search in the user's MIOpen directory (tuned_find_db), else config.  `config.miopen_find` in the result line says what ran")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.entry == "runner" and not args.full:
+        p.error("--entry runner needs --full")
+    return args
+
+
+def tuned_find_db():
+    """True if MIOpen's user directory holds a find-db: __graft_entry__.build() runs this benchmark's first step once with the
+    search on where it finds a GPU, and MIOpen records the winners there (and the compiled kernels in its cache)."""
+    import glob
+    d = os.environ.get("MIOPEN_USER_DB_PATH") or os.path.join(os.path.expanduser("~"), ".config", "miopen")
+    return bool(glob.glob(os.path.join(d, "*.ufdb.txt")))
 
 
 def build_model(cfg, device, channels_last):
@@ -334,6 +365,85 @@ def cpu_baseline(cfg_path, batch_size, steps):
                            cfg.model["name"], batch_size, gpu_batch, cfg.model["height"], cfg.model["width"], steps))
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6      # --dump-outputs: all files together, with room below 64 MB for the .npy headers
+
+
+def _flatten_named(prefix, value, out):
+    if torch.is_tensor(value):
+        if value.is_floating_point():
+            out.append((prefix, value))
+    elif isinstance(value, (list, tuple)):
+        for i, v in enumerate(value):
+            _flatten_named("%s_%d" % (prefix, i), v, out)
+
+
+def snapshot_state(model, step):
+    """Everything a training step reads and changes, copied: parameters (and the flat store's buffers), BatchNorm buffers and the
+    device's generator state.  Taken before the first step, when the optimiser's state is still all zeros."""
+    inner = model.module if hasattr(model, "module") else model
+    tensors = list(inner.parameters()) + list(inner.buffers())
+    if step.flat is not None:
+        tensors += [step.flat.flat_w, step.flat.flat_lp]
+    return [(t, t.detach().clone()) for t in tensors], torch.cuda.get_rng_state(step.device)
+
+
+def restore_state(snap, step):
+    """Copy a snapshot_state() back in place (a captured graph keeps reading the same tensors) and zero the optimiser's state."""
+    saved, rng = snap
+    with torch.no_grad():
+        for t, v in saved:
+            t.copy_(v)
+        for st in step.optimizer.state.values():
+            for v in st.values():
+                if torch.is_tensor(v):
+                    v.zero_()
+    torch.cuda.set_rng_state(rng, step.device)
+
+
+def dump_outputs(directory, step):
+    """What a caller of the timed step receives after its last iteration -- ``step.loss``, ``step.losses`` and the floating-point
+    entries of ``step.outputs`` -- one float32 ``<name>.npy`` each.  Together they stay under DUMP_BUDGET_BYTES: every array
+    larger than the common cap is reduced to the elements at a fixed, seeded set of flat indices (the same in every run).
+
+    Two runs agree to the rounding of the formats: one MIOpen forward kernel accumulates in an order that varies, so bf16
+    activations differ by one unit in the last place here and there (measured: disparities and reconstructions at most
+    2^-8, loss entries at most 1e-5).  Left out because they are not comparable at that level: the integer arg-min maps
+    (``min_index``: a tie at rounding level flips an entry by whole units; 2-4 pixels in 10 000 did) and the gradient norm
+    (the backward's atomic accumulations moved it by 0.5 %)."""
+    import re
+    import numpy as np
+    named = [("loss", step.loss)]
+    for k, v in step.losses.items():
+        _flatten_named("loss__" + (k if isinstance(k, str) else "_".join(str(x) for x in k)), v, named)
+    for k, v in step.outputs.items():
+        _flatten_named("out__" + (k if isinstance(k, str) else "_".join(str(x) for x in k)), v, named)
+    # the largest per-array element count such that the whole set fits the budget
+    budget = DUMP_BUDGET_BYTES // 4
+    sizes = sorted(t.numel() for _, t in named)
+    cap, left = None, budget
+    for i, n in enumerate(sizes):
+        share = left // (len(sizes) - i)
+        if n > share:
+            cap = share
+            break
+        left -= n
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, t in named:
+        name = re.sub(r"[^A-Za-z0-9_.-]+", "_", name)
+        flat = t.detach().reshape(-1)
+        if cap is not None and flat.numel() > cap:
+            g = torch.Generator(device="cpu").manual_seed(20240229)
+            idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+            arr = flat.to(torch.float32).cpu().numpy()
+        else:
+            arr = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), arr)
+        written[name] = list(arr.shape)
+    return written
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -353,8 +463,9 @@ def main():
         else:
             dist.init_process_group(backend)
     cfg = Config.fromfile(args.config)
-    torch.backends.cudnn.benchmark = {"config": bool(cfg.get("cudnn_benchmark", False)), "on": True,
-                                      "off": False}[args.miopen_find]
+    find = bool(cfg.get("cudnn_benchmark", False))
+    flagship = os.path.abspath(args.config) == os.path.join(ROOT, "config", "cfg_kitti_tripleD.py")      # what build() searched for
+    torch.backends.cudnn.benchmark = {"auto": find and not (flagship and tuned_find_db()), "config": find, "on": True, "off": False}[args.miopen_find]
     m = cfg.model
     if args.prune_extractor_tail:
         m["prune_extractor_tail"] = True
@@ -375,9 +486,10 @@ def main():
     # the same isolated kernel timing as the `roofline` block, taken BEFORE the training run (idle GPU): reported next to the
     # after-run figure, which stays the one `roofline.frac` is computed from
     kern_before = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         try:
-            kern_before = roofline_of_hot_kernels(cfg, batch)
+            with torch.random.fork_rng(devices=[dev]):      # the training run draws the same numbers with and without --full
+                kern_before = roofline_of_hot_kernels(cfg, batch)
         except Exception as e:      # noqa: BLE001 -- auxiliary figure
             kern_before = {"error": "%s: %s" % (type(e).__name__, e)}
     side = torch.cuda.Stream()
@@ -428,6 +540,7 @@ def main():
         elif mode == "single" and args.split_timing:
             flat_kind, split = "fp32", True
         st = TrainStep(wrapped, cfg, batch, dtype, flat=flat_kind)
+        initial = snapshot_state(net, st) if args.dump_outputs else None
         dispatch.hip_calls.clear()
         warm_up(st, max(args.warmup, 1), side)
         calls = sum(dispatch.hip_calls.values()) // max(args.warmup, 1)
@@ -443,7 +556,7 @@ def main():
             # captured but NOT replayed yet: under N > 1 a replay executes collectives, so it must not start before every
             # rank is known to have captured successfully (main loop below)
             gs = capture_step(st, stream=cap, split=split, capture_error_mode="thread_local" if dp else "global", validate=False)
-        return dict(mode=mode, model=net, step=st, graphed=gs, calls=calls, loss_after_warmup=after_warmup)
+        return dict(mode=mode, model=net, step=st, graphed=gs, calls=calls, loss_after_warmup=after_warmup, initial=initial)
 
     def trial_ms(cand, iters=5):
         run_ = cand["graphed"] if cand["graphed"] is not None else cand["step"]
@@ -487,7 +600,7 @@ def main():
     best = min(candidates, key=lambda c: trials.get(c["mode"], 0.0))
     used_mode, model, step, graphed_step = best["mode"], best["model"], best["step"], best["graphed"]
     graphed = graphed_step is not None
-    td_calls_per_step, loss_after_warmup = best["calls"], best["loss_after_warmup"]
+    td_calls_per_step, loss_after_warmup, initial = best["calls"], best["loss_after_warmup"], best["initial"]
     for c in candidates:
         if c is not best:
             c.clear()
@@ -546,12 +659,23 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    paused = 0.0
+    for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            # --dump-outputs: the step whose results are written starts from the state before the first warm-up step.  The
+            # trajectory up to here is not reproducible (MIOpen's atomic weight-gradient solvers and the feature warp's atomic
+            # scatter make every update differ at rounding level, and training amplifies that), so two runs would otherwise
+            # write different arrays for the same inputs.  The clock stands still while the state is copied back.
+            torch.cuda.synchronize()
+            t_pause = time.perf_counter()
+            restore_state(initial, step)
+            torch.cuda.synchronize()
+            paused += time.perf_counter() - t_pause
         run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -564,11 +688,14 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         raise SystemExit(3)
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, "rank%d" % rank), step)
+        print("rank %d: wrote %d arrays to %s" % (rank, len(dumped), args.dump_outputs), file=sys.stderr)
 
     # the same workload through train.py's path (train_mono -> Runner -> RunnerIteration).  N > 1: only on request -- a
     # failure there would involve collectives, and the headline line must not depend on it
     runner_ms, runner_err = None, None
-    if args.entry == "runner" or (args.entry == "both" and world == 1):
+    if args.full and (args.entry == "runner" or (args.entry == "both" and world == 1)):
         try:
             runner_ms = runner_entry(args, batch, world, dev)
         except NonFiniteLossError:
@@ -601,7 +728,7 @@ def main():
                               "eager": "bucketed RCCL all-reduce overlapped with backward (eager step)"}[used_mode],
                 "step_mode": used_mode, "step_mode_trials_ms": trials or None,
                 "h2d_in_step": args.h2d or False, "extractor_tail_pruned": bool(m.get("prune_extractor_tail", False)),
-                "capture_stream": CAPTURE_STREAM if graphed else None,
+                "capture_stream": CAPTURE_STREAM if graphed else None, "miopen_find": "search in the first step" if torch.backends.cudnn.benchmark else "immediate mode (user find-db)",
                 # tripled_amd.streams: auto-encoder and pose network on side streams beside the depth chain (parallel branches
                 # of the captured graph); off under the overlapped bucket engine, whose hooks assume one backward stream
                 "branch_streams": bool(__import__("tripled_amd.streams", fromlist=["ENABLED"]).ENABLED and getattr(model, "branch_streams", True)
@@ -617,7 +744,7 @@ def main():
                                             "resident in HBM, %d timed iterations" % args.steps}
         elif runner_err is not None:
             line["runner_entry"] = {"error": runner_err}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             kern = roofline_of_hot_kernels(cfg, batch)
             dom = max(kern, key=lambda k: kern[k]["seconds"])
             ach = kern[dom]["bytes"] / kern[dom]["seconds"] / 1e9
@@ -663,7 +790,7 @@ def main():
                     "mfma_busy_frac_of_step": round(busy / (ms * 1e-3 * mf["clock_ghz"] * 1e9 * mf["simds"]), 4),
                     "mfma_util_inside_conv_kernels": mf["mfma_util_conv_kernels"],
                     "mfma_util_inside_td_conv1x1": mf.get("mfma_util_td_conv1x1"), "source": mf["source"], "stamp": mf["_stamp"]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             del model, step, graph, graph_b, graphed_step, run
             torch.cuda.empty_cache()
             line["cpu_baseline"] = cpu_baseline(args.config, args.cpu_batch, args.cpu_steps)

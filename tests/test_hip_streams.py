@@ -142,7 +142,7 @@ def test_bench_replays_the_forked_step_from_a_hip_graph():
     a finite, moving loss with zero ATen fallbacks."""
     env = dict(os.environ)
     env.pop("TD_BRANCH_STREAMS", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline",
                           "--no-roofline", "--miopen-find", "off"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
