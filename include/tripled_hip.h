@@ -585,6 +585,37 @@ int td_fp8_amax_partials(const void* x, int dtype, long long n, float* partials,
 int td_fp8_quantize(const void* x, int dtype, long long n, const float* partials, uint8_t* q, float* inv_scale,
                     td_stream_t stream);
 
+/*
+ * Depth inference around the network forward (csrc/td_infer.hip).  Both resizes are ATen's upsample_bilinear2d with
+ * align_corners=False in float32: scale = (float)n_in / n_out, src = max(scale * (dst + 0.5f) - 0.5f, 0), i0 = (int)src,
+ * i1 = i0 + (i0 < n_in - 1), l1 = src - i0, l0 = 1 - l1, value = l0y (l0x p00 + l1x p01) + l1y (l0x p10 + l1x p11).
+ *
+ * td_infer_preprocess: image -> network input.  Replaces transform(), scripts/infer.py:25-30 (astype(float32), permute,
+ * F.interpolate(bilinear), /= 255), and -- with mirror = 1 -- the flipped second pass of the flip post-processing.
+ *   img_u8 [B,H0,W0,3] uint8, interleaved RGB;  out [B*(1+mirror),3,h,w] float32 (out)
+ *   mirror = 1: out[B+n,:,y,x] = out[n,:,y,w-1-x]
+ *
+ * td_disp_postprocess: network disparity -> full-size disparity and depth in one launch.  Replaces predict(),
+ * scripts/infer.py:41-46 (F.interpolate to the image size, depth = SCALE / (disp * max_disp + min_disp)) and
+ * batch_post_process_disparity, scripts/eval_depth_pp.py:22-28.
+ *   disp [B*(1+paired),1,h,w], dtype TD_DTYPE_F32 / TD_DTYPE_BF16
+ *   paired = 1: every bilinear tap is  r_mask l + l_mask r + (1 - l_mask - r_mask) 0.5 (l + r)  with l = disp[n,0,y,x],
+ *               r = disp[B+n,0,y,w-1-x], l_mask(x) = 1 - clip(20 (x / (w-1) - 0.05), 0, 1), r_mask(x) = l_mask(w-1-x)  (w >= 2)
+ *   disp_out [B,H0,W0] (out);  depth_out [B,H0,W0] = depth_scale / (a * disp_out + b) (out, may be NULL)
+ *   scripts/infer.py: a = 1/1e-3, b = 1/80, depth_scale = 36;  disp_to_depth(., 0.1, 100): a = 1/0.1 - 1/100, b = 1/100, 1.
+ *
+ * td_colorize: value -> colour through a 256-entry table.  Replaces plt.imsave(path, disp, cmap='magma',
+ * vmax=np.percentile(disp, 95)), scripts/infer.py:65-66 (the caller computes vmin / vmax).
+ *   x [B,n] float32;  vmin, vmax [B] (device);  lut [256,3] uint8 (device);  out [B,n,3] uint8 (out)
+ *   index = clamp((int)floorf(((x - vmin) / (vmax - vmin)) * 256.f), 0, 255), every step a rounded float32 operation.
+ */
+int td_infer_preprocess(const uint8_t* img_u8, int B, int H0, int W0, int h, int w, int mirror, float* out,
+                        td_stream_t stream);
+int td_disp_postprocess(const void* disp, int dtype, int B, int h, int w, int paired, int H0, int W0, float a, float b,
+                        float depth_scale, float* disp_out, float* depth_out, td_stream_t stream);
+int td_colorize(const float* x, int B, long long n, const float* vmin, const float* vmax, const uint8_t* lut, uint8_t* out,
+                td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

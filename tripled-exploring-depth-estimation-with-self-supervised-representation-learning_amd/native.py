@@ -108,6 +108,9 @@ SIGNATURES = {
     "td_rgb2lab": (_I, [_P, _I, _I, _I, _F, _F, _F, _P, _P]),
     "td_pose_fwd": (_I, [_P, _P, _IARR, _P, _I, _I, _P, _P, _P]),
     "td_pose_bwd": (_I, [_P, _P, _IARR, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "td_infer_preprocess": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
+    "td_disp_postprocess": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),
+    "td_colorize": (_I, [_P, _I, ctypes.c_longlong, _P, _P, _P, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
