@@ -616,6 +616,39 @@ int td_disp_postprocess(const void* disp, int dtype, int B, int h, int w, int pa
 int td_colorize(const float* x, int B, long long n, const float* vmin, const float* vmax, const uint8_t* lut, uint8_t* out,
                 td_stream_t stream);
 
+/*
+ * KITTI depth evaluation of a batch on the device (csrc/td_eval.hip).  Replaces, per image, the protocol of
+ * scripts/eval_depth.py:73-101 = mono/core/evaluation/eval_hooks.py:225-262 (cv2.resize of the scaled disparity to the
+ * ground-truth size, 1 / ., mask min < gt < max inside the Garg crop, np.median ratio (x 36 for stereo), clip, compute_errors).
+ *
+ * td_eval_depth: 10 launches whatever B is, no synchronisation, no copy to the host, no allocation.
+ *   disp [B,h,w], dtype TD_DTYPE_F32 / TD_DTYPE_BF16: the sigmoid disparity;  scaled = b + a * disp (float32; disp_to_depth(.,
+ *        0.1, 100): a = 9.99, b = 0.01; (1, 0) for an already scaled disparity)
+ *   gt [B,Hmax,Wmax] float32: image i occupies the top-left sizes[i] = (gt_h, gt_w); the padding never enters
+ *   sizes [B,2] int32 (device);  crops [B,4] int32 (device): (y0, y1, x0, x1), half-open, computed by the caller in float64 as
+ *        the host path does (np.array([0.40810811 gt_h, 0.99189189 gt_h, 0.03594771 gt_w, 0.96405229 gt_w]).astype(int32))
+ *   resize: source coordinate (q + 0.5) * (n_in / n_out) - 0.5 in double, floor, both taps clipped to the border; the affine is
+ *        applied to the four taps, the interpolation (rows, then columns) is float32
+ *   pred = 1 / resized;  N = pixels in the mask;  scale = median(gt) / median(pred), np.median's of the float32 values (even N:
+ *        0.5f * (lower + upper));  pred *= stereo ? TD_STEREO_SCALE_FACTOR : scale;  clip to [min_depth, max_depth]
+ *   metrics [B,8] (out): abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, scale;  counts [B] int32 (out): N.  N = 0: a NaN row.
+ *   workspace: td_eval_depth_workspace_bytes(B, Hmax, Wmax) bytes, 8-byte aligned (TD_ERR_WORKSPACE if workspace_bytes is less)
+ *   Sums are accumulated in double per block and added in a fixed order; the select uses integer atomics only: two calls on the
+ *   same inputs return the same bits.
+ *
+ * td_masked_median: the exact select on its own.  values [B,n] float32, an entry <= 0 (or NaN) is absent;
+ *   median [B] (out) = np.median of the row's present entries (NaN if none), count [B] int32 (out);
+ *   workspace: td_masked_median_workspace_bytes(B) bytes, 4-byte aligned.
+ */
+#define TD_STEREO_SCALE_FACTOR 36
+long long td_eval_depth_workspace_bytes(int B, int Hmax, int Wmax);
+int td_eval_depth(const void* disp, int dtype, int B, int h, int w, float a, float b, const float* gt, int Hmax, int Wmax,
+                  const int* sizes, const int* crops, float min_depth, float max_depth, int stereo, void* workspace,
+                  long long workspace_bytes, float* metrics, int* counts, td_stream_t stream);
+long long td_masked_median_workspace_bytes(int B);
+int td_masked_median(const float* values, int B, long long n, void* workspace, long long workspace_bytes, float* median,
+                     int* count, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,10 @@ disparity of every validation frame, resize to the ground-truth size, median-sca
 [1e-3, 80] inside the Garg crop and print the seven standard metrics.
 
   python scripts/eval_depth.py --config config/cfg_kitti_tripleD.py --checkpoint work/epoch_20.pth \
-         --gt_depths /data/kitti_raw/gt_depths.npz
+         --gt_depths /data/kitti_raw/gt_depths.npz [--batch_size 12 [--precision bf16] [--post_process]]
+
+--batch_size N scores N frames per launch chain on the device (tripled_amd.evaluate.DepthEvaluator, csrc/td_eval.hip); the
+default, 0, is the loop below.
 """
 import argparse
 import os
@@ -38,13 +41,26 @@ def evaluate(model, dataset, stereo_scale=False, device="cuda"):
     return mean, np.array([r["scale"] for r in results])
 
 
+def evaluate_batched(model, dataset, stereo_scale=False, device="cuda", batch_size=12, precision="fp32", post_process=False):
+    """evaluate() in batches through tripled_amd.evaluate.DepthEvaluator: scored on the device by td_eval_depth."""
+    from tripled_amd.evaluate import DepthEvaluator
+    return DepthEvaluator(model.eval().to(device), device, batch_size=batch_size, precision=precision, post_process=post_process,
+                          stereo_scale=stereo_scale).evaluate(dataset)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True)
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--gt_depths", default=None)
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--batch_size", type=int, default=0,
+                    help="0: one frame at a time, scored on the host; N > 0: batches of N scored on the device (DepthEvaluator)")
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32", help="with --batch_size: the forward's precision")
+    ap.add_argument("--post_process", action="store_true", help="with --batch_size: flip post-processing (eval_depth_pp.py)")
     args = ap.parse_args()
+    if args.batch_size <= 0 and (args.precision != "fp32" or args.post_process):
+        ap.error("--precision bf16 and --post_process belong to the batched path: give --batch_size N")
     cfg = Config.fromfile(args.config)
     if args.gt_depths:
         cfg.data["gt_depth_path"] = args.gt_depths
@@ -52,7 +68,11 @@ def main():
     model = MONO.module_dict[cfg.model["name"]](cfg.model)
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True)      # executes nothing from the file
     model.load_state_dict(ckpt["state_dict"], strict=True)
-    mean, ratios = evaluate(model, get_dataset(cfg.data, training=False), bool(cfg.data["stereo_scale"]), args.device)
+    dataset, stereo = get_dataset(cfg.data, training=False), bool(cfg.data["stereo_scale"])
+    if args.batch_size > 0:
+        mean, ratios = evaluate_batched(model, dataset, stereo, args.device, args.batch_size, args.precision, args.post_process)
+    else:
+        mean, ratios = evaluate(model, dataset, stereo, args.device)
     med = np.median(ratios)
     print("Scaling ratios | med: {:0.3f} | std: {:0.3f}".format(med, np.std(ratios / med)))
     print("\n  " + ("{:>8} | " * 7).format(*METRICS))

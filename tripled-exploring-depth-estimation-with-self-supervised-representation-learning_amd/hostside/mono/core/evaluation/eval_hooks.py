@@ -86,6 +86,22 @@ def _predict_one(model, sample):
     return scaled.cpu()[0, 0].numpy(), gt
 
 
+def _evaluate_on_device(model, dataset, indices, stereo, cfg):
+    """cfg.validate_on_device: the frames ``indices`` in batches of cfg.validate_batch_size through
+    tripled_amd.evaluate.DepthEvaluator (scored by td_eval_depth, one copy to the host at the end), under the same
+    full-precision context as _predict_one.  Returns {index: per-image metric dict}, as the default loop builds."""
+    from tripled_amd.evaluate import COLUMNS, DepthEvaluator
+    dev = next(model.parameters()).device
+    inner = model.module if hasattr(model, "module") else model
+    flat = getattr(inner, "_flat_store", None)
+    ctx = flat.full_precision() if flat is not None else contextlib.nullcontext()
+    indices = list(indices)
+    with ctx:
+        rows, _ = DepthEvaluator(model, dev, batch_size=int(cfg.get("validate_batch_size", 12)),
+                                 stereo_scale=stereo).evaluate_rows(dataset, indices)
+    return {i: dict(zip(COLUMNS, (float(v) for v in row))) for i, row in zip(indices, rows)}
+
+
 def _publish(runner, results):
     meters = {k: AverageMeter() for k in METRICS + ("scale",)}
     for r in results:
@@ -113,9 +129,13 @@ class NonDistEvalHook(Hook):
         runner.model.eval()
         stereo = bool(self.cfg.data["stereo_scale"])
         results = []
-        for idx in range(len(self.dataset)):
-            disp, gt = _predict_one(runner.model, self.dataset[idx])
-            results.append(evaluate_disparity(disp, gt, stereo))
+        if self.cfg.get("validate_on_device", False):
+            scored = _evaluate_on_device(runner.model, self.dataset, range(len(self.dataset)), stereo, self.cfg)
+            results = [scored[i] for i in sorted(scored)]
+        else:
+            for idx in range(len(self.dataset)):
+                disp, gt = _predict_one(runner.model, self.dataset[idx])
+                results.append(evaluate_disparity(disp, gt, stereo))
         _publish(runner, results)
 
 
@@ -131,9 +151,13 @@ class DistEvalHook(Hook):
         stereo = bool(self.cfg.data["stereo_scale"])
         mine = {}
         t0 = time.time()
-        for idx in range(runner.rank, len(self.dataset), runner.world_size):   # reference :212
-            disp, gt = _predict_one(runner.model, self.dataset[idx])
-            mine[idx] = evaluate_disparity(disp, gt, stereo)
+        share = range(runner.rank, len(self.dataset), runner.world_size)      # reference :212
+        if self.cfg.get("validate_on_device", False):
+            mine = _evaluate_on_device(runner.model, self.dataset, share, stereo, self.cfg)
+        else:
+            for idx in share:
+                disp, gt = _predict_one(runner.model, self.dataset[idx])
+                mine[idx] = evaluate_disparity(disp, gt, stereo)
         fps = len(mine) / max(time.time() - t0, 1e-9)
         if runner.world_size > 1:
             gathered = [None] * runner.world_size

@@ -111,6 +111,10 @@ SIGNATURES = {
     "td_infer_preprocess": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
     "td_disp_postprocess": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),
     "td_colorize": (_I, [_P, _I, ctypes.c_longlong, _P, _P, _P, _P, _P]),
+    "td_eval_depth_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
+    "td_eval_depth": (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _I, _I, _P, _P, _F, _F, _I, _P, ctypes.c_longlong, _P, _P, _P]),
+    "td_masked_median_workspace_bytes": (ctypes.c_longlong, [_I]),
+    "td_masked_median": (_I, [_P, _I, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
