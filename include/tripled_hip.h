@@ -649,6 +649,49 @@ long long td_masked_median_workspace_bytes(int B);
 int td_masked_median(const float* values, int B, long long n, void* workspace, long long workspace_bytes, float* median,
                      int* count, td_stream_t stream);
 
+/*
+ * KITTI odometry evaluation on the device (csrc/td_odom.hip).  All pose arithmetic is float64 (float32 inputs are widened
+ * exactly), sums have a fixed order and there are no floating-point atomics: two calls on the same inputs return the same bits.
+ *
+ * td_pose_pairs_u8: the pose network's input.  Replaces torch.cat([inputs[("color_aug", i, 0)] for i in [0, 1]], 1) on ToTensor
+ * frames, scripts/eval_pose.py:59 (= scripts/draw_odometry.py:69), without decoding or uploading any frame twice.
+ *   frames [n+1,3,H,W] uint8 (device);  pair i = cat(frame i, frame i+1) along the channels, each byte float(b) / 255 (a float32
+ *   division), stored as dtype TD_DTYPE_F32 / TD_DTYPE_BF16 (round to nearest even).  Pairs [first, first+count) are written to
+ *   rows out_first .. out_first+count-1 of out [.,6,H,W]: out_first = first fills a window of the full [n,6,H,W] array,
+ *   out_first = 0 a batch buffer.  8 bytes per thread where 3 H W is a multiple of 8 (and the bases are aligned), else scalar.
+ *
+ * td_odom_trajectory: relative transforms -> global poses.  Replaces the loop global_pose = global_pose @ np.linalg.inv(g),
+ * scripts/draw_odometry.py:62-74.
+ *   rel [n,4,4] float32 (rel_f64 = 0) or float64 (1): frame k+1 -> frame k;  poses [n+1,3,4] float64 (out): G_0 = I,
+ *   G_{k+1} = G_k inv(M_k), inv = the affine inverse (3x3 by cofactors, -A^-1 t), not the transpose.  One workgroup: every thread
+ *   composes a contiguous chunk in order, an LDS scan of the chunk totals keeps left-to-right order.  Any n >= 1.
+ *
+ * td_odom_snippet_ate: replaces scripts/eval_pose.py:66-80 with dump_xyz and compute_ate, mono/datasets/utils.py:105-122.
+ *   rel as above (the PREDICTED relative transforms);  gt_poses [n+1,3,4] float64;  track_length 2..16 (the reference: 5)
+ *   ates [n] float64 (out): snippet i covers transforms i .. min(i + track_length - 1, n) - 1; gt local transforms are
+ *   inv(inv(G_{k}) G_{k+1}); positions are cumulative products of the transforms themselves; the least-squares scale
+ *   sum(gt * pred) / sum(pred^2) (0 / 0 = NaN); sqrt(sum err^2) / (the snippet's own point count).  One thread per snippet.
+ *
+ * td_odom_sequence_errors: replaces kittiOdomEval.eval's core, mono/tools/kitti_evaluation_toolkit.py:109-182 (trajectoryDistances,
+ * lastFrameFromSegmentLength, calcSequenceErrors) and align_trajectory(correct_only_scale=True), mono/tools/trajectory.py:367-402
+ * with geometry.umeyama_alignment, mono/tools/geometry.py:20-67.
+ *   gt_poses, pred_poses [m,3,4] float64;  lengths: HOST array of n_lengths <= 16 positive segment lengths;  step: first frames
+ *   are 0, step, 2 step, ... (F = ceil(m / step) of them)
+ *   align_scale = 1: c = trace(diag(d) S) / sigma_x of the predicted against the ground-truth positions (singular values of the
+ *        3x3 covariance by one-sided Jacobi, fixed sweep count; S's last entry = sign(det(cov))) scales the predicted translations
+ *   dist [m] float64 (out / workspace): cumulative ground-truth distance, accumulated sequentially in index order
+ *   rows [F,n_lengths,5] float64 (out): first_frame, r_err / len, t_err / len, len, speed;  valid [F,n_lengths] uint8 (out): 0 where
+ *        no frame lies more than len beyond first_frame (the row's errors and speed are then NaN)
+ *   summary [2] float64 (out): c (1 without align_scale), total ground-truth distance
+ */
+int td_pose_pairs_u8(const uint8_t* frames, int n, int H, int W, int first, int count, int dtype, void* out, long long out_first,
+                     td_stream_t stream);
+int td_odom_trajectory(const void* rel, int rel_f64, int n, double* poses, td_stream_t stream);
+int td_odom_snippet_ate(const void* rel, int rel_f64, const double* gt_poses, int n, int track_length, double* ates,
+                        td_stream_t stream);
+int td_odom_sequence_errors(const double* gt_poses, const double* pred_poses, int m, const double* lengths, int n_lengths, int step,
+                            int align_scale, double* dist, double* rows, uint8_t* valid, double* summary, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

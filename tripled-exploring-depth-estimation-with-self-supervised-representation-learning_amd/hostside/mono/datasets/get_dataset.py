@@ -37,4 +37,16 @@ def get_dataset(cfg, training=True):
         return cls(in_path, filenames, cfg["height"], cfg["width"], cfg["frame_ids"] if training else [0],
                    is_train=training, img_ext=".png" if cfg.get("png", True) else ".jpg",
                    gt_depth_path=cfg.get("gt_depth_path", None), cfg=cfg)
+    if name == "kitti_odom":
+        # odometry evaluation (scripts/eval_pose.py): cfg.sequence + cfg.n_frames name the pairs, or cfg.split_file lists them
+        from .kitti_dataset import KITTIOdomDataset, odom_sequence_files
+        if not have_data:
+            raise FileNotFoundError("dataset 'kitti_odom': in_path %r is not a directory" % (in_path,))
+        if cfg.get("split_file", None):
+            with open(cfg["split_file"]) as f:
+                filenames = f.read().splitlines()
+        else:
+            filenames = odom_sequence_files(cfg["sequence"], cfg["n_frames"])
+        return KITTIOdomDataset(in_path, filenames, cfg["height"], cfg["width"], cfg.get("frame_ids", [0, 1]), is_train=False,
+                                img_ext=".png" if cfg.get("png", True) else ".jpg", gt_depth_path=None, cfg=cfg)
     raise NotImplementedError("dataset '%s' is outside the KITTI depth training path" % name)

@@ -108,6 +108,15 @@ class MonoDataset(Dataset):
     def postprocess(self, inputs):
         """Hook for subclasses (in-painting masks)."""
 
+    def frame_u8(self, index, offset=0):
+        """The frame ``offset`` after the one line ``index`` names, decoded once and resized like a sample's frames: uint8
+        [3,H,W], no augmentation.  A consumer that needs every frame of a sequence (tripled_amd.odometry) reads n+1 frames this way
+        instead of n samples of two frames each."""
+        parts = self.filenames[index].split()
+        frame_index = int(parts[1]) if len(parts) == 3 else 0
+        side = parts[2] if len(parts) == 3 else None
+        return to_uint8(self.resize(self.get_color(parts[0], frame_index + offset, side, False)))
+
     def __getitem__(self, index):
         inputs = {}
         do_color_aug = self.is_train and random.random() > 0.5
@@ -192,3 +201,21 @@ class KITTIInpaintDataset(KITTIDataset):
                 col = int(torch.randint(0, image.shape[2] - ew - 1, (1,)))
                 mask[:, row:row + eh, col:col + ew] = 0
         inputs[("mask", 0, 0)] = mask
+
+
+class KITTIOdomDataset(KITTIDataset):
+    """KITTI odometry sequences (reference kitti_dataset.py:324-338): <data_path>/sequences/<NN>/image_<0|1>/<%06d><ext>; the
+    folder field of a line is the sequence number."""
+    side_map = {"l": 0, "r": 1}
+
+    def get_image_path(self, folder, frame_index, side):
+        name = "{:06d}{}".format(frame_index, self.img_ext)
+        return os.path.join(self.data_path, "sequences/{:02d}".format(int(folder)), "image_{}".format(self.side_map[side]), name)
+
+
+def odom_sequence_files(seq, n_frames):
+    """The lines "<seq> <i> l" for i in 0 ... n_frames-2: one per consecutive frame pair of a sequence of n_frames frames (the
+    contents of the reference's splits/odom/test_files_09.txt / _10.txt for n_frames = 1591 / 1201)."""
+    if int(n_frames) < 2:
+        raise ValueError("a sequence needs at least two frames, got %r" % (n_frames,))
+    return ["{} {} l".format(int(seq), i) for i in range(int(n_frames) - 1)]

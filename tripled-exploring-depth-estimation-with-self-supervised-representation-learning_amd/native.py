@@ -115,6 +115,10 @@ SIGNATURES = {
     "td_eval_depth": (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _I, _I, _P, _P, _F, _F, _I, _P, ctypes.c_longlong, _P, _P, _P]),
     "td_masked_median_workspace_bytes": (ctypes.c_longlong, [_I]),
     "td_masked_median": (_I, [_P, _I, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _P]),
+    "td_pose_pairs_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P]),
+    "td_odom_trajectory": (_I, [_P, _I, _I, _P, _P]),
+    "td_odom_snippet_ate": (_I, [_P, _I, _P, _I, _I, _P, _P]),
+    "td_odom_sequence_errors": (_I, [_P, _P, _I, ctypes.POINTER(ctypes.c_double), _I, _I, _I, _P, _P, _P, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
