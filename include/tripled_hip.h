@@ -692,6 +692,27 @@ int td_odom_snippet_ate(const void* rel, int rel_f64, const double* gt_poses, in
 int td_odom_sequence_errors(const double* gt_poses, const double* pred_poses, int m, const double* lengths, int n_lengths, int step,
                             int align_scale, double* dist, double* rows, uint8_t* valid, double* summary, td_stream_t stream);
 
+/*
+ * Resize and flip of uint8 frames on the device, bit-equal to Pillow's Image.resize((W, H), LANCZOS) after
+ * Image.transpose(FLIP_LEFT_RIGHT) (csrc/td_resize.hip).  Replaces MonoDataset's per-frame resize and flip in the loader workers,
+ * mono/datasets/mono_dataset.py:60-63,129-143, for the "raw_u8" wire format.  One launch, no synchronisation, no allocation.
+ *   src [N,3,Hc,Wc] uint8 (4-byte aligned): image n occupies the top-left (h, w) of its canvas, the size its size index names;
+ *        no byte outside that region enters a result
+ *   meta [N,2] int32 (device): (size index, flip).  An index outside [0, n_sizes) zero-fills that image and sets status[0] = 1.
+ *   meta_host: the same array on the host, or NULL; when given, an index out of range is TD_ERR_BAD_ARG before any launch
+ *   tables: int32 device buffer of table_ints ints;  desc: HOST int32 [n_sizes,8] = (h, w, ksx, ksy, off_kx, off_bx, off_ky, off_by),
+ *        offsets in ints into tables: horizontal coefficients TRANSPOSED [ksx,W], horizontal bounds [W,2] = (first, count),
+ *        vertical coefficients [H,ksy], vertical bounds [H,2]; 22-bit fixed point, |k| < 2^23 (tripled_amd/resize.py: LanczosBank)
+ *   a pass:  out = clamp((2^21 + sum_t k[t] * pixel[first + t]) >> 22, 0, 255), int32; horizontal (reading column w - 1 - (first + t)
+ *        with flip), a uint8 intermediate, then vertical
+ *   dst [N,3,H,W] uint8 (out);  status [1] int32 (device): written only on a bad index (1) or tables that do not fit the sizes (2)
+ *   TD_ERR_BAD_ARG: n_sizes outside 1..16, a size larger than the canvas, offsets outside the buffer, a bad index in meta_host.
+ *   TD_ERR_UNSUPPORTED: rows too wide for the LDS tile, N > 65535, a misaligned src.
+ */
+int td_lanczos_resize_u8(const uint8_t* src, const int* meta, const int* meta_host, const int* tables, long long table_ints,
+                         const int* desc, int n_sizes, int N, int Hc, int Wc, int H, int W, uint8_t* dst, int* status,
+                         td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import infer, native
+from . import infer, native, resize
 
 METRICS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 COLUMNS = METRICS + ("scale",)
@@ -192,6 +192,12 @@ def _collate(samples, device, on_hip):
     batch = {}
     for k in samples[0]:
         stacked = torch.stack([torch.as_tensor(s[k]) for s in samples], 0)
+        if k == "raw_spec":                              # 'raw_u8' wire format: read by the host in the expansion
+            batch[k] = stacked
+            continue
+        if k == "raw_meta" or (isinstance(k, tuple) and k and k[0] == "raw_u8"):
+            batch[k] = stacked.to(device)                # bytes / int32; resized by the HIP kernel (a host batch raises there)
+            continue
         if isinstance(k, tuple) and k and k[0] == "color_u8":
             if on_hip:
                 batch[k] = stacked.to(device)
@@ -200,7 +206,7 @@ def _collate(samples, device, on_hip):
                 batch[("color", k[1], 0)], batch[("color_aug", k[1], 0)] = img, img
             continue
         batch[k] = stacked.float().to(device)
-    if on_hip:
+    if on_hip or "raw_meta" in batch:
         from mono.datasets import expand_device_batch
         expand_device_batch(batch)
     batch.pop("aug", None)
@@ -291,6 +297,8 @@ class DepthEvaluator:
                 rows.append(m)
                 counts.append(c)
         rows, counts = torch.cat(rows, 0).cpu().numpy(), torch.cat(counts, 0).cpu().numpy()          # the one copy
+        if self.on_hip:
+            resize.check_banks()          # 'raw_u8' wire format: a frame the resize kernel zero-filled raises here (no bank: no read)
         empty = np.nonzero(counts == 0)[0]
         if len(empty):
             raise ValueError("frame %d: no ground-truth pixel inside the crop and the depth range" % indices[int(empty[0])])

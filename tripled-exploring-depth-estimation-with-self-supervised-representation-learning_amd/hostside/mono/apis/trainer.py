@@ -4,7 +4,7 @@ from collections import OrderedDict
 
 import torch
 from mmcv.parallel import MMDataParallel, MMDistributedDataParallel
-from mmcv.runner import DistSamplerSeedHook, Runner, obj_from_dict
+from mmcv.runner import DistSamplerSeedHook, Hook, Runner, obj_from_dict
 
 from mono.core import DistEvalMonoHook, DistOptimizerHook, NonDistEvalHook
 from mono.datasets import build_dataloader
@@ -57,9 +57,12 @@ def configure_execution(model, cfg, dev):
 def stage_inputs(data):
     """Every entry of the batch dict -> float32 on the training device (frames of the 'uint8' wire format stay bytes).
     The copies are issued non-blocking (asynchronous when the loader pins memory; no-ops behind DevicePrefetcher)."""
+    from mono.datasets.raw_wire import HOST_KEYS, is_byte_frame
     dev = _device()
     for k, v in data.items():
-        if isinstance(k, tuple) and k and k[0] == "color_u8":       # 'uint8' wire format: bytes until expanded on the device
+        if k in HOST_KEYS:                                          # 'raw_u8' wire format: read by the host in the expansion
+            continue
+        if is_byte_frame(k) or k == "raw_meta":                     # byte wire formats: bytes (int32) until expanded on the device
             data[k] = torch.as_tensor(v).to(dev, non_blocking=True)
         elif "kp" not in k:
             data[k] = torch.as_tensor(v).to(dev, dtype=torch.float32, non_blocking=True)
@@ -223,7 +226,20 @@ def _maybe_prefetch(loaders, cfg):
     return loaders
 
 
+class RawWireStatusHook(Hook):
+    """'raw_u8' wire format: a size index outside the coefficient bank cannot be reported by the captured iteration (the index
+    lives on the device; the kernel zero-fills the frame and raises the bank's status word).  The end of an epoch -- after the
+    validation hooks, which expand their batches the same way -- reads the word back and raises.  Nothing to read without a bank."""
+
+    def after_train_epoch(self, runner):
+        if torch.cuda.is_available():
+            from tripled_amd import resize
+            resize.check_banks()
+
+
 def _finish_runner(runner, cfg, data_loaders):
+    if (cfg.get("data", None) or {}).get("wire", "float32") == "raw_u8":
+        runner.register_hook(RawWireStatusHook(), priority="LOWEST")
     data_loaders = _maybe_prefetch(data_loaders, cfg)
     if cfg.resume_from:
         runner.resume(cfg.resume_from)

@@ -64,6 +64,12 @@ def _predict_one(model, sample):
     batch = {}
     for k, v in sample.items():
         t = torch.as_tensor(v)
+        if k == "raw_spec":                              # 'raw_u8' wire format: read by the host in the expansion
+            batch[k] = t.unsqueeze(0)
+            continue
+        if k == "raw_meta" or (isinstance(k, tuple) and k and k[0] == "raw_u8"):
+            batch[k] = t.unsqueeze(0).to(dev)            # bytes / int32; resized by the HIP kernel (no host path: a CPU model raises)
+            continue
         if isinstance(k, tuple) and k and k[0] == "color_u8":
             if dev.type == "cuda":                       # 'uint8' wire format: expanded by the HIP kernel below
                 batch[k] = t.unsqueeze(0).to(dev)
@@ -72,7 +78,7 @@ def _predict_one(model, sample):
                 batch[("color", k[1], 0)], batch[("color_aug", k[1], 0)] = img, img
             continue
         batch[k] = t.float().unsqueeze(0).to(dev)
-    if dev.type == "cuda":
+    if dev.type == "cuda" or "raw_meta" in batch:
         from mono.datasets import expand_device_batch
         expand_device_batch(batch)
     batch.pop("aug", None)

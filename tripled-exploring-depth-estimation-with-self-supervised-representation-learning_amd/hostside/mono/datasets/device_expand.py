@@ -1,28 +1,61 @@
-"""Device-side expansion of the 'uint8' wire format (cfg.data.wire = "uint8").
+"""Device-side expansion of the byte wire formats (cfg.data.wire = "uint8" / "raw_u8").
 
-The loader ships ("color_u8", f) uint8 [B,3,H,W] per frame and "aug" [B,9] (one colour-jitter draw per sample, shared
+"uint8": the loader ships ("color_u8", f) uint8 [B,3,H,W] per frame and "aug" [B,9] (one colour-jitter draw per sample, shared
 by its frames as in the reference, mono/datasets/mono_dataset.py:89-95); one HIP launch pair turns them into the
 ("color", f, 0) / ("color_aug", f, 0) float tensors the models consume (csrc/td_augment.hip).  The host->device copy
-is 3 bytes per pixel and frame instead of 24, and ToTensor + ColorJitter leave the loader workers."""
+is 3 bytes per pixel and frame instead of 24, and ToTensor + ColorJitter leave the loader workers.
+
+"raw_u8": the loader ships ("raw_u8", f) uint8 [B,3,Hc,Wc] -- the decoded frames at their native size on a canvas -- with
+"raw_meta" int32 [B,2] and "raw_spec" (mono.datasets.raw_wire); one more launch in front (csrc/td_resize.hip) flips and resizes them
+to the bytes PIL's LANCZOS resize gives, and the flip and the resize leave the loader workers too.  The network size and the size list
+come from "raw_spec", which stays on the host: the expansion looks the cached coefficient bank up without touching the device, so it
+runs inside the captured training graph (the bank itself is built in the eager warm-up iterations, tripled_amd.resize.get_bank).
+Two limits follow.  "raw_spec" is a host value, so a captured graph bakes in the bank found at capture time: replays do not run this
+function and keep that bank whatever later batches carry, i.e. one run has one (H, W, raw_sizes).  And "raw_meta" is a device value
+the host never reads here: a size index outside the bank zero-fills the frame and raises the bank's status word, which the trainer
+reads at the end of an epoch and DepthEvaluator after its copy to the host (tripled_amd.resize.check_banks); other callers poll it."""
 import torch
+
+from .raw_wire import parse_spec
+
+
+def _frame_keys(data, tag):
+    return sorted((k for k in data if isinstance(k, tuple) and k and k[0] == tag), key=lambda k: str(k[1]))
 
 
 def has_uint8_frames(data):
     return isinstance(data, dict) and any(isinstance(k, tuple) and k and k[0] == "color_u8" for k in data)
 
 
+def has_raw_frames(data):
+    return isinstance(data, dict) and any(isinstance(k, tuple) and k and k[0] == "raw_u8" for k in data)
+
+
 def expand_device_batch(data):
-    """In place: replaces the ("color_u8", f) / "aug" entries of a device-resident batch dict."""
-    if not has_uint8_frames(data):
+    """In place: replaces the ("color_u8", f) or ("raw_u8", f) / "raw_meta" / "raw_spec" entries, and "aug", of a device-resident
+    batch dict."""
+    raw = has_raw_frames(data)
+    if not raw and not has_uint8_frames(data):
         return data
     from tripled_amd import native, ops
-    frames = sorted((k for k in data if isinstance(k, tuple) and k[0] == "color_u8"), key=lambda k: str(k[1]))
+    frames = _frame_keys(data, "raw_u8" if raw else "color_u8")
     first = data[frames[0]]
     if not first.is_cuda:
-        raise native.NativeLibraryError("the uint8 wire format is expanded by a HIP kernel: move the batch to the device first "
-                                        "(or load with wire='float32')")
+        raise native.NativeLibraryError("the %s wire format is expanded by a HIP kernel: move the batch to the device first "
+                                        "(or load with wire='float32')" % ("raw_u8" if raw else "uint8"))
     B = first.shape[0]
-    stacked = torch.cat([data[k] for k in frames], 0)                       # [F*B,3,H,W] uint8
+    stacked = torch.cat([data[k] for k in frames], 0)                       # [F*B,3,H,W] uint8 (raw: [F*B,3,Hc,Wc])
+    if raw:
+        from tripled_amd import resize
+        spec = data["raw_spec"]                                              # a host tensor: no synchronisation
+        if spec.is_cuda or spec.dim() != 2 or not bool((spec == spec[0]).all()):
+            raise ValueError("'raw_spec' must stay on the host and be one configuration per batch: samples of datasets with different "
+                             "sizes or raw_sizes cannot share a batch")
+        height, width, sizes = parse_spec(spec[0])
+        bank = resize.get_bank(sizes, height, width, first.device)
+        meta = data["raw_meta"].to(torch.int32).repeat(len(frames), 1)       # the frames of a sample share size and flip
+        stacked = resize.lanczos_resize_hip(stacked, meta, bank)
+        del data["raw_meta"], data["raw_spec"]
     aug = data["aug"].float().repeat(len(frames), 1)                         # the frames of a sample share its draw
     color, color_aug = ops.color_jitter_expand(stacked, aug)
     for i, k in enumerate(frames):

@@ -16,6 +16,8 @@ import torch
 from PIL import Image, ImageEnhance
 from torch.utils.data import Dataset
 
+from . import raw_wire as raw_wire_mod
+
 LANCZOS = getattr(Image, "Resampling", Image).LANCZOS
 FLIP = getattr(Image, "Transpose", Image).FLIP_LEFT_RIGHT
 
@@ -92,6 +94,7 @@ class MonoDataset(Dataset):
         self.gt_depth_path = gt_depth_path
         self.flag = np.zeros(len(self), dtype=np.int64)        # single aspect-ratio group for the samplers
         self.gt_depths = None
+        self._raw = None
         if not is_train and gt_depth_path is not None and os.path.exists(str(gt_depth_path)):
             # the reference loads this archive with allow_pickle=True; object arrays are refused here
             self.gt_depths = np.load(gt_depth_path, allow_pickle=False)["data"]
@@ -104,6 +107,13 @@ class MonoDataset(Dataset):
 
     def get_color(self, folder, frame_index, side, do_flip):
         raise NotImplementedError
+
+    def _raw_layout(self):
+        """(sizes, canvas, "raw_spec") of the 'raw_u8' wire format: fixed by the configuration, worked out once."""
+        if self._raw is None:
+            sizes = raw_wire_mod.raw_sizes_of(self.cfg)
+            self._raw = (sizes, raw_wire_mod.canvas_of(sizes), raw_wire_mod.raw_spec(self.height, self.width, sizes))
+        return self._raw
 
     def postprocess(self, inputs):
         """Hook for subclasses (in-painting masks)."""
@@ -130,23 +140,40 @@ class MonoDataset(Dataset):
         jitter = ColorJitter(self.brightness, self.contrast, self.saturation, self.hue) if do_color_aug else None
         # wire = "uint8": frames travel as bytes, ToTensor and the colour jitter run on the device
         # (mono.datasets.device_expand / csrc/td_augment.hip); "float32" is the reference's format
-        u8_wire = self.cfg.get("wire", "float32") == "uint8"
+        # wire = "raw_u8": the frames travel at their native size; the flip and the LANCZOS resize run on the device too
+        # (mono.datasets.raw_wire / csrc/td_resize.hip), with the same draws in the same order
+        wire = self.cfg.get("wire", "float32")
+        raw_wire = wire == "raw_u8"
+        u8_wire = wire == "uint8" or raw_wire
         if u8_wire:
             inputs["aug"] = jitter.as_row() if jitter is not None else torch.zeros(9)
+        load_flipped = do_flip and not raw_wire
+        raw_index = None
+        sizes, canvas, spec = self._raw_layout() if raw_wire else (None, None, None)
         for i in self.frame_idxs:
             if i == "s":
-                img = self.get_color(folder, frame_index, {"r": "l", "l": "r"}[side], do_flip)
+                img = self.get_color(folder, frame_index, {"r": "l", "l": "r"}[side], load_flipped)
             else:
                 try:
-                    img = self.get_color(folder, frame_index + i, side, do_flip)
+                    img = self.get_color(folder, frame_index + i, side, load_flipped)
                 except (FileNotFoundError, OSError):            # sequence boundary: repeat the centre frame
-                    img = self.get_color(folder, frame_index, side, do_flip)
+                    img = self.get_color(folder, frame_index, side, load_flipped)
+            if raw_wire:
+                idx = raw_wire_mod.size_index(img.height, img.width, sizes)
+                if raw_index is not None and idx != raw_index:
+                    raise ValueError("the frames of sample %d have different sizes: 'raw_meta' is one size index per sample" % index)
+                raw_index = idx
+                inputs[("raw_u8", i)] = raw_wire_mod.to_canvas(to_uint8(img), canvas)
+                continue
             img = self.resize(img)
             if u8_wire:
                 inputs[("color_u8", i)] = to_uint8(img)
                 continue
             inputs[("color", i, 0)] = to_tensor(img)
             inputs[("color_aug", i, 0)] = to_tensor(jitter(img)) if jitter is not None else inputs[("color", i, 0)].clone()
+        if raw_wire:
+            inputs["raw_meta"] = torch.tensor([raw_index, int(do_flip)], dtype=torch.int32)
+            inputs["raw_spec"] = spec.clone()
         K = self.K.copy()
         K[0, :] *= self.width
         K[1, :] *= self.height
@@ -188,17 +215,20 @@ class KITTIInpaintDataset(KITTIDataset):
     erase_count == 1), reference kitti_dataset.py:167-182."""
 
     def postprocess(self, inputs):
-        image = inputs[("color", 0, 0)] if ("color", 0, 0) in inputs else inputs[("color_u8", 0)]
+        if ("raw_u8", 0) in inputs:                 # 'raw_u8' wire: the frame is still a canvas; the mask has the network size
+            shape = (3, self.height, self.width)
+        else:
+            shape = tuple((inputs[("color", 0, 0)] if ("color", 0, 0) in inputs else inputs[("color_u8", 0)]).shape)
         eh, ew = self.cfg["erase_shape"]
         count = self.cfg["erase_count"]
-        mask = torch.ones(image.shape, dtype=torch.uint8)
+        mask = torch.ones(shape, dtype=torch.uint8)
         if count == 1:
-            off = int((image.shape[1] - eh) / 2)
+            off = int((shape[1] - eh) / 2)
             mask[:, off:off + eh, off:off + eh] = 0
         else:
             for _ in range(count):
-                row = int(torch.randint(0, image.shape[1] - eh - 1, (1,)))
-                col = int(torch.randint(0, image.shape[2] - ew - 1, (1,)))
+                row = int(torch.randint(0, shape[1] - eh - 1, (1,)))
+                col = int(torch.randint(0, shape[2] - ew - 1, (1,)))
                 mask[:, row:row + eh, col:col + ew] = 0
         inputs[("mask", 0, 0)] = mask
 

@@ -6,6 +6,8 @@ handed over already on the device (float32; uint8 frames of the 'uint8' wire for
 ``mono.datasets.device_expand`` in batch_processor), so ``change_input_variable`` finds nothing left to copy."""
 import torch
 
+from .raw_wire import HOST_KEYS, is_byte_frame
+
 
 class DevicePrefetcher:
     def __init__(self, loader, device=None):
@@ -21,12 +23,14 @@ class DevicePrefetcher:
         out = {}
         with torch.cuda.stream(self.stream):
             for k, v in batch.items():
-                if isinstance(v, torch.Tensor):
+                if isinstance(v, torch.Tensor) and k in HOST_KEYS:
+                    out[k] = v                  # read by the host in the device-side expansion (raw_wire.py)
+                elif isinstance(v, torch.Tensor):
                     if not v.is_pinned():
                         v = v.pin_memory()
                     v = v.to(self.device, non_blocking=True)
-                    # the uint8 wire format stays bytes until the device-side expansion (device_expand.py)
-                    out[k] = v if (isinstance(k, tuple) and k and k[0] == "color_u8") else v.float()
+                    # the byte wire formats stay bytes (and "raw_meta" int32) until the device-side expansion (device_expand.py)
+                    out[k] = v if (is_byte_frame(k) or k == "raw_meta") else v.float()
                 else:
                     out[k] = v
         return out
@@ -41,7 +45,7 @@ class DevicePrefetcher:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
             cur = nxt
             for v in cur.values():
-                if isinstance(v, torch.Tensor):
+                if isinstance(v, torch.Tensor) and v.is_cuda:
                     v.record_stream(torch.cuda.current_stream(self.device))
             try:
                 nxt = self._stage(next(it))

@@ -26,13 +26,37 @@ def _smooth_canvas(g, h, w):
     return img.clamp_(0, 1)
 
 
+def _pil_flip_resize(frame_chw_u8, height, width, flip):
+    """What the KITTI loader does to a decoded frame: transpose(FLIP_LEFT_RIGHT), then resize((width, height), LANCZOS)."""
+    from .kitti_dataset import FLIP, LANCZOS, to_uint8
+    from PIL import Image
+    img = Image.fromarray(frame_chw_u8.permute(1, 2, 0).contiguous().numpy())
+    img = img.transpose(FLIP) if flip else img
+    return to_uint8(img.resize((width, height), LANCZOS))
+
+
 def make_sample(seed, height, width, frame_ids=(0, -1, 1), erase_shape=(16, 16), erase_count=16, max_shift=4,
-                with_mask=True, wire="float32", augment=False, coherent=True):
+                with_mask=True, wire="float32", augment=False, coherent=True, raw_sizes=None):
     """coherent=False: every frame is independent U[0,1) noise -- the adversarial input of SURVEY.md section 8d
-    (no frame explains another, so the arg-min and the bilinear taps see uncorrelated values)."""
+    (no frame explains another, so the arg-min and the bilinear taps see uncorrelated values).
+
+    raw_sizes (a list of (h, w); the KITTI sizes for wire="raw_u8" without one): the frames are generated at the NATIVE size
+    raw_sizes[seed % n] and a flip is drawn for an augmented sample, as the KITTI loader does.  wire="raw_u8" ships them on a canvas
+    with "raw_meta" / "raw_spec" (mono.datasets.raw_wire); wire="uint8" flips and resizes them on the host with PIL LANCZOS, so the two
+    wires carry the same frames."""
     g = torch.Generator().manual_seed(int(seed))
-    canvas = _smooth_canvas(g, height + 2 * max_shift, width + 2 * max_shift)
+    if wire == "raw_u8" or raw_sizes is not None:
+        if wire not in ("raw_u8", "uint8"):
+            raise ValueError("raw_sizes needs wire='raw_u8' or 'uint8', got %r" % (wire,))
+        from . import raw_wire
+        sizes = raw_wire.raw_sizes_of({"raw_sizes": raw_sizes})
+        size_idx = int(seed) % len(sizes)
+        gen_h, gen_w = sizes[size_idx]
+    else:
+        sizes, (gen_h, gen_w) = None, (height, width)
+    canvas = _smooth_canvas(g, gen_h + 2 * max_shift, gen_w + 2 * max_shift)
     sample = {}
+    frames_u8 = {}
     for f in frame_ids:
         if f == 0:
             dy = dx = max_shift
@@ -40,21 +64,34 @@ def make_sample(seed, height, width, frame_ids=(0, -1, 1), erase_shape=(16, 16),
             dy = int(torch.randint(0, 2 * max_shift + 1, (1,), generator=g))
             dx = int(torch.randint(0, 2 * max_shift + 1, (1,), generator=g))
         if coherent:
-            img = canvas[:, dy:dy + height, dx:dx + width].contiguous()
+            img = canvas[:, dy:dy + gen_h, dx:dx + gen_w].contiguous()
         else:
-            img = torch.rand(3, height, width, generator=g)
-        if wire == "uint8":      # the byte wire format of the KITTI loader (kitti_dataset.py), expanded on the device
-            sample[("color_u8", f)] = (img * 255.0).round().clamp_(0, 255).to(torch.uint8)
+            img = torch.rand(3, gen_h, gen_w, generator=g)
+        if wire in ("uint8", "raw_u8"):      # the byte wire formats of the KITTI loader (kitti_dataset.py), expanded on the device
+            u8 = (img * 255.0).round().clamp_(0, 255).to(torch.uint8)
+            if sizes is None:
+                sample[("color_u8", f)] = u8
+            else:
+                frames_u8[f] = u8       # native size: shipped (or resized on the host) once the flip is drawn
             continue
         sample[("color", f, 0)] = img
         sample[("color_aug", f, 0)] = img.clone()
-    if wire == "uint8":
+    if wire in ("uint8", "raw_u8"):
         row = torch.zeros(9)
         if augment and float(torch.rand(1, generator=g)) > 0.5:
             u = lambda lo, hi: lo + (hi - lo) * float(torch.rand(1, generator=g))
             row = torch.tensor([1.0] + [float(v) for v in torch.randperm(4, generator=g)] +
                                [u(0.8, 1.2), u(0.8, 1.2), u(0.8, 1.2), u(-0.1, 0.1)])
         sample["aug"] = row
+        flip = bool(sizes is not None and augment and float(torch.rand(1, generator=g)) > 0.5)
+        for f, u8 in frames_u8.items():
+            if wire == "raw_u8":
+                sample[("raw_u8", f)] = raw_wire.to_canvas(u8, raw_wire.canvas_of(sizes))
+            else:
+                sample[("color_u8", f)] = _pil_flip_resize(u8, height, width, flip)
+        if wire == "raw_u8":
+            sample["raw_meta"] = torch.tensor([size_idx, int(flip)], dtype=torch.int32)
+            sample["raw_spec"] = raw_wire.raw_spec(height, width, sizes)
     if with_mask:
         mask = torch.ones(3, height, width)
         eh, ew = erase_shape
@@ -71,8 +108,8 @@ def make_sample(seed, height, width, frame_ids=(0, -1, 1), erase_shape=(16, 16),
 
 class SyntheticTripletDataset(Dataset):
     def __init__(self, length, height, width, frame_ids=(0, -1, 1), erase_shape=(16, 16), erase_count=16,
-                 seed=1000, with_mask=True, with_gt=False, wire="float32", augment=False):
-        self.wire, self.augment = wire, augment
+                 seed=1000, with_mask=True, with_gt=False, wire="float32", augment=False, raw_sizes=None):
+        self.wire, self.augment, self.raw_sizes = wire, augment, raw_sizes
         self.length, self.height, self.width = length, height, width
         self.frame_ids, self.erase_shape, self.erase_count = tuple(frame_ids), tuple(erase_shape), erase_count
         self.seed, self.with_mask, self.with_gt = seed, with_mask, with_gt
@@ -83,7 +120,8 @@ class SyntheticTripletDataset(Dataset):
 
     def __getitem__(self, idx):
         s = make_sample(self.seed + idx, self.height, self.width, self.frame_ids, self.erase_shape,
-                        self.erase_count, with_mask=self.with_mask, wire=self.wire, augment=self.augment)
+                        self.erase_count, with_mask=self.with_mask, wire=self.wire, augment=self.augment,
+                        raw_sizes=self.raw_sizes)
         if self.with_gt:
             g = torch.Generator().manual_seed(self.seed + idx + 7)
             s["gt_depth"] = 2.0 + 60.0 * torch.rand(self.height, self.width, generator=g)
