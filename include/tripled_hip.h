@@ -706,12 +706,28 @@ int td_odom_sequence_errors(const double* gt_poses, const double* pred_poses, in
  *   a pass:  out = clamp((2^21 + sum_t k[t] * pixel[first + t]) >> 22, 0, 255), int32; horizontal (reading column w - 1 - (first + t)
  *        with flip), a uint8 intermediate, then vertical
  *   dst [N,3,H,W] uint8 (out);  status [1] int32 (device): written only on a bad index (1) or tables that do not fit the sizes (2)
+ *        (3: td_lanczos_resize_u8_indexed, below)
  *   TD_ERR_BAD_ARG: n_sizes outside 1..16, a size larger than the canvas, offsets outside the buffer, a bad index in meta_host.
  *   TD_ERR_UNSUPPORTED: rows too wide for the LDS tile, N > 65535, a misaligned src.
  */
 int td_lanczos_resize_u8(const uint8_t* src, const int* meta, const int* meta_host, const int* tables, long long table_ints,
                          const int* desc, int n_sizes, int N, int Hc, int Wc, int H, int W, uint8_t* dst, int* status,
                          td_stream_t stream);
+
+/*
+ * The same resize and flip with the sources fetched from a byte store resident in device memory (the "resident" wire format,
+ * tripled_amd/resident.py): image n is planar uint8 [3,h,w] at byte offsets[n] of the store, rows tight (stride w), (h, w) the size
+ * its size index names.  Arithmetic, tables, dst and the meaning of meta, meta_host, tables, desc are those of the call above.
+ *   store: store_bytes bytes (4-byte aligned base); the offsets themselves may have any alignment
+ *   offsets [N] int64 (device).  An offset that is negative or with offset + 3 h w > store_bytes zero-fills that image and sets
+ *        status[0] = 3; no byte outside [store, store + store_bytes) is ever read
+ *   offsets_host: the same array on the host, or NULL; when given, such an offset is TD_ERR_BAD_ARG before any launch (checked against
+ *        the frame's own size when meta_host is given too, against the smallest size of the bank otherwise)
+ *   TD_ERR_UNSUPPORTED: rows of the widest size too wide for the LDS tile, N > 65535, a misaligned store.
+ */
+int td_lanczos_resize_u8_indexed(const uint8_t* store, long long store_bytes, const long long* offsets, const long long* offsets_host,
+                                 const int* meta, const int* meta_host, const int* tables, long long table_ints, const int* desc,
+                                 int n_sizes, int N, int H, int W, uint8_t* dst, int* status, td_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -19,7 +19,15 @@
 // Only the top-left (h, w) of a canvas enters a result.  The kernel does not rely on the tables for that: source columns are clamped to
 // [0, w - 1] and source rows to [r0, min(.., h)) against the sizes in the launch arguments, which the entry point checks against the
 // canvas, so tables of another size give wrong bytes inside the valid region at worst, never a read outside it.
+//
+// Two entry points share the body through a small address functor.  td_lanczos_resize_u8 reads canvases [N,3,Hc,Wc].
+// td_lanczos_resize_u8_indexed (the "resident" wire format) reads planar frames [3,h,w] with tight rows at per-image int64 byte offsets
+// of one store: rows of odd width start on every byte phase, which the dword staging already carries, and the byte-wise tail is that of
+// the store.  An offset whose frame would leave the store is refused by the block before it reads anything (status 3, zero-filled).
 #include "td_common.h"
+
+#include <algorithm>
+#include <climits>
 
 #define TD_RESIZE_MAX_SIZES 16
 
@@ -43,12 +51,41 @@ __device__ __forceinline__ void zero_band(uint8_t* __restrict__ out, int y0, int
   for (int i = threadIdx.x; i < n; i += RS_THREADS) out[(size_t)y0 * W + i] = 0;
 }
 
-__global__ __launch_bounds__(RS_THREADS) void lanczos_resize_kernel(const uint8_t* __restrict__ src, const int* __restrict__ meta,
-                                                                    const int* __restrict__ tables, const ResizeBank bank, int n_sizes,
-                                                                    int Hc, int Wc, int H, int W, int band, int span_max, int Wp, int SW,
-                                                                    long long total_bytes, int packed_store, uint8_t* __restrict__ dst,
-                                                                    int* __restrict__ status) {
-  extern __shared__ __align__(16) unsigned char lds[];
+// Where image n, channel c lies.  ``locate`` gives the valid size (h, w), the byte offset of the plane in ``src`` and its row stride;
+// false: the image cannot be read (zero-filled, status 3).  Everything after it is shared by the two entry points.
+struct CanvasSource {                        // td_lanczos_resize_u8: [N,3,Hc,Wc], the image in the top-left of its canvas
+  int Hc, Wc;
+  __device__ __forceinline__ bool locate(int n, int c, const ResizeDesc& d, int& h, int& w, size_t& plane, int& stride) const {
+    h = min(d.h, Hc);
+    w = min(d.w, Wc);
+    plane = (size_t)(n * 3 + c) * Hc * Wc;
+    stride = Wc;
+    return true;
+  }
+};
+
+struct StoreSource {                         // td_lanczos_resize_u8_indexed: planar [3,h,w] at offsets[n] of a byte store, rows tight
+  const long long* __restrict__ offsets;
+  long long bytes;
+  __device__ __forceinline__ bool locate(int n, int c, const ResizeDesc& d, int& h, int& w, size_t& plane, int& stride) const {
+    h = d.h;
+    w = d.w;
+    stride = d.w;
+    const long long off = offsets[n];
+    const long long frame = 3ll * d.h * d.w;
+    plane = 0;
+    if (off < 0 || frame > bytes || off > bytes - frame) return false;       // the frame would leave the store: nothing is read
+    plane = (size_t)off + (size_t)c * d.h * d.w;
+    return true;
+  }
+};
+
+template <class Source>
+__device__ __forceinline__ void lanczos_resize_body(unsigned char* lds, const uint8_t* __restrict__ src, const Source source,
+                                                    const int* __restrict__ meta, const int* __restrict__ tables, const ResizeBank& bank,
+                                                    int n_sizes, int H, int W, int band, int span_max, int Wp, int SW,
+                                                    long long total_bytes, int packed_store, uint8_t* __restrict__ dst,
+                                                    int* __restrict__ status) {
   unsigned char* stage = lds;                        // [RS_ROWS][SW]: source rows, each at its byte phase
   unsigned char* tile = lds + RS_ROWS * SW;          // [span_max][Wp]: horizontally resampled rows r0 ...
   const int n = blockIdx.z, c = blockIdx.y;
@@ -63,7 +100,13 @@ __global__ __launch_bounds__(RS_THREADS) void lanczos_resize_kernel(const uint8_
     return;
   }
   const ResizeDesc d = bank.d[s];
-  const int h = min(d.h, Hc), w = min(d.w, Wc);
+  int h, w, stride;
+  size_t plane;
+  if (!source.locate(n, c, d, h, w, plane, stride)) {
+    zero_band(out, y0, y1, W);
+    if (threadIdx.x == 0) status[0] = 3;
+    return;
+  }
   const int* __restrict__ kxT = tables + d.off_kx;   // [ksx][W]
   const int* __restrict__ bx = tables + d.off_bx;    // [W][2]
   const int* __restrict__ ky = tables + d.off_ky;    // [H][ksy]
@@ -75,7 +118,6 @@ __global__ __launch_bounds__(RS_THREADS) void lanczos_resize_kernel(const uint8_
     if (threadIdx.x == 0) status[0] = 2;
     return;
   }
-  const size_t plane = (size_t)(n * 3 + c) * Hc * Wc;
   const int DW = SW >> 2;
   const uint32_t* __restrict__ src32 = reinterpret_cast<const uint32_t*>(src);
 
@@ -84,7 +126,7 @@ __global__ __launch_bounds__(RS_THREADS) void lanczos_resize_kernel(const uint8_
     // ---- stage nr source rows: aligned dwords covering [base, base + w) of each row
     for (int idx = threadIdx.x; idx < nr * DW; idx += RS_THREADS) {
       const int r = idx / DW, j = idx - r * DW;
-      const size_t base = plane + (size_t)(rs + r) * Wc;
+      const size_t base = plane + (size_t)(rs + r) * stride;
       const int ndw = ((int)(base & 3) + w + 3) >> 2;
       if (j >= ndw) continue;
       const size_t di = (base >> 2) + j;
@@ -101,7 +143,7 @@ __global__ __launch_bounds__(RS_THREADS) void lanczos_resize_kernel(const uint8_
     // ---- horizontal pass: one thread = one output column x all staged rows
     int roff[RS_ROWS];
 #pragma unroll
-    for (int r = 0; r < RS_ROWS; ++r) roff[r] = r * SW + (int)((plane + (size_t)(rs + r) * Wc) & 3);
+    for (int r = 0; r < RS_ROWS; ++r) roff[r] = r * SW + (int)((plane + (size_t)(rs + r) * stride) & 3);
     for (int x = threadIdx.x; x < W; x += RS_THREADS) {
       const int xmin = bx[2 * x], cnt = min(bx[2 * x + 1], d.ksx);
       int acc[RS_ROWS];
@@ -157,6 +199,73 @@ __global__ __launch_bounds__(RS_THREADS) void lanczos_resize_kernel(const uint8_
   }
 }
 
+__global__ __launch_bounds__(RS_THREADS) void lanczos_resize_kernel(const uint8_t* __restrict__ src, const int* __restrict__ meta,
+                                                                    const int* __restrict__ tables, const ResizeBank bank, int n_sizes,
+                                                                    int Hc, int Wc, int H, int W, int band, int span_max, int Wp, int SW,
+                                                                    long long total_bytes, int packed_store, uint8_t* __restrict__ dst,
+                                                                    int* __restrict__ status) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  lanczos_resize_body(lds, src, CanvasSource{Hc, Wc}, meta, tables, bank, n_sizes, H, W, band, span_max, Wp, SW, total_bytes,
+                      packed_store, dst, status);
+}
+
+__global__ __launch_bounds__(RS_THREADS) void lanczos_resize_indexed_kernel(const uint8_t* __restrict__ store, long long store_bytes,
+                                                                            const long long* __restrict__ offsets,
+                                                                            const int* __restrict__ meta, const int* __restrict__ tables,
+                                                                            const ResizeBank bank, int n_sizes, int H, int W, int band,
+                                                                            int span_max, int Wp, int SW, int packed_store,
+                                                                            uint8_t* __restrict__ dst, int* __restrict__ status) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  lanczos_resize_body(lds, store, StoreSource{offsets, store_bytes}, meta, tables, bank, n_sizes, H, W, band, span_max, Wp, SW,
+                      store_bytes, packed_store, dst, status);
+}
+
+// The launch geometry both entry points share.  ``h_max`` x ``w_max`` bounds every source the launch can meet (the canvas, or the
+// largest size of the bank): the staging rows are as wide as w_max, and no band needs more tile rows than h_max.
+struct ResizePlan { ResizeBank bank; int band, span_max, Wp, SW, bands; size_t lds; };
+
+static int plan_resize(const int* desc, int n_sizes, long long table_ints, int H, int W, int h_limit, int w_limit, int* h_max, int* w_max,
+                       ResizePlan* plan) {
+  if (n_sizes < 1 || n_sizes > TD_RESIZE_MAX_SIZES) return TD_ERR_BAD_ARG;
+  plan->bank = {};
+  double max_scale_y = 0.0;
+  int max_ksy = 1, hm = 0, wm = 0;
+  for (int i = 0; i < n_sizes; ++i) {
+    ResizeDesc& d = plan->bank.d[i];
+    const int* p = desc + 8 * i;
+    d.h = p[0]; d.w = p[1]; d.ksx = p[2]; d.ksy = p[3]; d.off_kx = p[4]; d.off_bx = p[5]; d.off_ky = p[6]; d.off_by = p[7];
+    if (d.h < 1 || d.w < 1 || d.h > h_limit || d.w > w_limit || d.ksx < 1 || d.ksy < 1) return TD_ERR_BAD_ARG;   // a size larger than the canvas
+    if (d.off_kx < 0 || d.off_bx < 0 || d.off_ky < 0 || d.off_by < 0) return TD_ERR_BAD_ARG;
+    if ((long long)d.off_kx + (long long)d.ksx * W > table_ints || (long long)d.off_bx + 2ll * W > table_ints ||
+        (long long)d.off_ky + (long long)d.ksy * H > table_ints || (long long)d.off_by + 2ll * H > table_ints)
+      return TD_ERR_BAD_ARG;
+    const double sy = (double)d.h / (double)H;
+    if (sy > max_scale_y) max_scale_y = sy;
+    if (d.ksy > max_ksy) max_ksy = d.ksy;
+    if (d.h > hm) hm = d.h;
+    if (d.w > wm) wm = d.w;
+  }
+  if (*h_max <= 0) *h_max = hm;
+  if (*w_max <= 0) *w_max = wm;
+  if ((long long)H * W >= (1ll << 30) || (long long)*h_max * *w_max >= (1ll << 30)) return TD_ERR_UNSUPPORTED;
+  plan->Wp = (W + 3) & ~3;
+  plan->SW = ((*w_max + 3) & ~3) + 8;
+  // rows of the tile a band needs: the first rows of its first and last output row lie <= ceil((band - 1) scale) + 1 apart, the
+  // last row adds its taps
+  plan->band = 0;
+  plan->span_max = 0;
+  for (int b = 16; b >= 1; b >>= 1) {
+    long long span = (long long)ceil((double)(b - 1) * max_scale_y) + 1 + max_ksy;
+    if (span > *h_max) span = *h_max;
+    if ((long long)RS_ROWS * plan->SW + span * plan->Wp <= RS_LDS_BUDGET) { plan->band = b; plan->span_max = (int)span; break; }
+  }
+  if (plan->band == 0) return TD_ERR_UNSUPPORTED;    // rows too wide for the tile
+  plan->bands = (H + plan->band - 1) / plan->band;
+  if (plan->bands > 65535) return TD_ERR_UNSUPPORTED;
+  plan->lds = (size_t)RS_ROWS * plan->SW + (size_t)plan->span_max * plan->Wp;
+  return TD_OK;
+}
+
 }  // namespace td
 
 extern "C" int td_lanczos_resize_u8(const uint8_t* src, const int* meta, const int* meta_host, const int* tables, long long table_ints,
@@ -165,44 +274,51 @@ extern "C" int td_lanczos_resize_u8(const uint8_t* src, const int* meta, const i
   if (!src || !meta || !tables || !desc || !dst || !status || N <= 0 || Hc <= 0 || Wc <= 0 || H <= 0 || W <= 0 || table_ints <= 0)
     return TD_ERR_BAD_ARG;
   if (n_sizes < 1 || n_sizes > TD_RESIZE_MAX_SIZES) return TD_ERR_BAD_ARG;
-  td::ResizeBank bank = {};
-  double max_scale_y = 0.0;
-  int max_ksy = 1;
-  for (int i = 0; i < n_sizes; ++i) {
-    td::ResizeDesc& d = bank.d[i];
-    const int* p = desc + 8 * i;
-    d.h = p[0]; d.w = p[1]; d.ksx = p[2]; d.ksy = p[3]; d.off_kx = p[4]; d.off_bx = p[5]; d.off_ky = p[6]; d.off_by = p[7];
-    if (d.h < 1 || d.w < 1 || d.h > Hc || d.w > Wc || d.ksx < 1 || d.ksy < 1) return TD_ERR_BAD_ARG;   // a size larger than the canvas
-    if (d.off_kx < 0 || d.off_bx < 0 || d.off_ky < 0 || d.off_by < 0) return TD_ERR_BAD_ARG;
-    if ((long long)d.off_kx + (long long)d.ksx * W > table_ints || (long long)d.off_bx + 2ll * W > table_ints ||
-        (long long)d.off_ky + (long long)d.ksy * H > table_ints || (long long)d.off_by + 2ll * H > table_ints)
-      return TD_ERR_BAD_ARG;
-    const double sy = (double)d.h / (double)H;
-    if (sy > max_scale_y) max_scale_y = sy;
-    if (d.ksy > max_ksy) max_ksy = d.ksy;
-  }
   if (meta_host)
     for (int n = 0; n < N; ++n)
       if (meta_host[2 * n] < 0 || meta_host[2 * n] >= n_sizes) return TD_ERR_BAD_ARG;
+  td::ResizePlan plan;
+  int h_max = Hc, w_max = Wc;
+  const int rc = td::plan_resize(desc, n_sizes, table_ints, H, W, Hc, Wc, &h_max, &w_max, &plan);
+  if (rc == TD_ERR_BAD_ARG) return rc;
   if (((uintptr_t)src & 3u) || N > 65535) return TD_ERR_UNSUPPORTED;
+  if (rc != TD_OK) return rc;
   const long long total = (long long)N * 3 * Hc * Wc;
-  if ((long long)H * W >= (1ll << 30) || (long long)Hc * Wc >= (1ll << 30)) return TD_ERR_UNSUPPORTED;
-  const int Wp = (W + 3) & ~3;
-  const int SW = ((Wc + 3) & ~3) + 8;
-  // rows of the tile a band needs: the first rows of its first and last output row lie <= ceil((band - 1) scale) + 1 apart, the
-  // last row adds its taps
-  int band = 0, span_max = 0;
-  for (int b = 16; b >= 1; b >>= 1) {
-    long long span = (long long)ceil((double)(b - 1) * max_scale_y) + 1 + max_ksy;
-    if (span > Hc) span = Hc;
-    if ((long long)td::RS_ROWS * SW + span * Wp <= td::RS_LDS_BUDGET) { band = b; span_max = (int)span; break; }
-  }
-  if (band == 0) return TD_ERR_UNSUPPORTED;          // rows too wide for the tile
-  const int bands = (H + band - 1) / band;
-  if (bands > 65535) return TD_ERR_UNSUPPORTED;
   const int packed = ((W & 3) == 0 && ((uintptr_t)dst & 3u) == 0) ? 1 : 0;
-  const size_t lds = (size_t)td::RS_ROWS * SW + (size_t)span_max * Wp;
-  hipLaunchKernelGGL(td::lanczos_resize_kernel, dim3(bands, 3, N), dim3(td::RS_THREADS), lds, (hipStream_t)stream, src, meta, tables, bank,
-                     n_sizes, Hc, Wc, H, W, band, span_max, Wp, SW, total, packed, dst, status);
+  hipLaunchKernelGGL(td::lanczos_resize_kernel, dim3(plan.bands, 3, N), dim3(td::RS_THREADS), plan.lds, (hipStream_t)stream, src, meta,
+                     tables, plan.bank, n_sizes, Hc, Wc, H, W, plan.band, plan.span_max, plan.Wp, plan.SW, total, packed, dst, status);
   return td::record_launch_error(hipGetLastError(), "td_lanczos_resize_u8");
+}
+
+extern "C" int td_lanczos_resize_u8_indexed(const uint8_t* store, long long store_bytes, const long long* offsets,
+                                            const long long* offsets_host, const int* meta, const int* meta_host, const int* tables,
+                                            long long table_ints, const int* desc, int n_sizes, int N, int H, int W, uint8_t* dst,
+                                            int* status, td_stream_t stream) {
+  if (!store || !offsets || !meta || !tables || !desc || !dst || !status || store_bytes <= 0 || N <= 0 || H <= 0 || W <= 0 ||
+      table_ints <= 0)
+    return TD_ERR_BAD_ARG;
+  if (n_sizes < 1 || n_sizes > TD_RESIZE_MAX_SIZES) return TD_ERR_BAD_ARG;
+  if (meta_host)
+    for (int n = 0; n < N; ++n)
+      if (meta_host[2 * n] < 0 || meta_host[2 * n] >= n_sizes) return TD_ERR_BAD_ARG;
+  td::ResizePlan plan;
+  int h_max = 0, w_max = 0;                          // no canvas: the largest size of the bank
+  const int rc = td::plan_resize(desc, n_sizes, table_ints, H, W, INT_MAX, INT_MAX, &h_max, &w_max, &plan);
+  if (rc == TD_ERR_BAD_ARG) return rc;
+  if (offsets_host) {
+    // with the size indices the whole frame is checked; without them, the smallest frame of the bank (a necessary condition)
+    long long least = LLONG_MAX;
+    for (int i = 0; i < n_sizes; ++i) least = std::min(least, 3ll * plan.bank.d[i].h * plan.bank.d[i].w);
+    for (int n = 0; n < N; ++n) {
+      const long long frame = meta_host ? 3ll * plan.bank.d[meta_host[2 * n]].h * plan.bank.d[meta_host[2 * n]].w : least;
+      if (offsets_host[n] < 0 || frame > store_bytes || offsets_host[n] > store_bytes - frame) return TD_ERR_BAD_ARG;
+    }
+  }
+  if (((uintptr_t)store & 3u) || N > 65535) return TD_ERR_UNSUPPORTED;
+  if (rc != TD_OK) return rc;
+  const int packed = ((W & 3) == 0 && ((uintptr_t)dst & 3u) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(td::lanczos_resize_indexed_kernel, dim3(plan.bands, 3, N), dim3(td::RS_THREADS), plan.lds, (hipStream_t)stream, store,
+                     store_bytes, offsets, meta, tables, plan.bank, n_sizes, H, W, plan.band, plan.span_max, plan.Wp, plan.SW, packed, dst,
+                     status);
+  return td::record_launch_error(hipGetLastError(), "td_lanczos_resize_u8_indexed");
 }

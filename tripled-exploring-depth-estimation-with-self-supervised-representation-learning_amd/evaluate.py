@@ -192,10 +192,10 @@ def _collate(samples, device, on_hip):
     batch = {}
     for k in samples[0]:
         stacked = torch.stack([torch.as_tensor(s[k]) for s in samples], 0)
-        if k == "raw_spec":                              # 'raw_u8' wire format: read by the host in the expansion
+        if k in ("raw_spec", "res_bytes"):               # raw_wire.HOST_KEYS: read by the host in the expansion
             batch[k] = stacked
             continue
-        if k == "raw_meta" or (isinstance(k, tuple) and k and k[0] == "raw_u8"):
+        if k == "raw_meta" or (isinstance(k, tuple) and k and k[0] in ("raw_u8", "res_off")):
             batch[k] = stacked.to(device)                # bytes / int32; resized by the HIP kernel (a host batch raises there)
             continue
         if isinstance(k, tuple) and k and k[0] == "color_u8":

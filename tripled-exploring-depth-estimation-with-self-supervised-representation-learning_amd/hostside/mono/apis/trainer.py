@@ -57,12 +57,12 @@ def configure_execution(model, cfg, dev):
 def stage_inputs(data):
     """Every entry of the batch dict -> float32 on the training device (frames of the 'uint8' wire format stay bytes).
     The copies are issued non-blocking (asynchronous when the loader pins memory; no-ops behind DevicePrefetcher)."""
-    from mono.datasets.raw_wire import HOST_KEYS, is_byte_frame
+    from mono.datasets.raw_wire import HOST_KEYS, keeps_dtype
     dev = _device()
     for k, v in data.items():
         if k in HOST_KEYS:                                          # 'raw_u8' wire format: read by the host in the expansion
             continue
-        if is_byte_frame(k) or k == "raw_meta":                     # byte wire formats: bytes (int32) until expanded on the device
+        if keeps_dtype(k):                                          # byte wire formats: bytes (int32, int64 offsets) until expanded
             data[k] = torch.as_tensor(v).to(dev, non_blocking=True)
         elif "kp" not in k:
             data[k] = torch.as_tensor(v).to(dev, dtype=torch.float32, non_blocking=True)
@@ -227,8 +227,9 @@ def _maybe_prefetch(loaders, cfg):
 
 
 class RawWireStatusHook(Hook):
-    """'raw_u8' wire format: a size index outside the coefficient bank cannot be reported by the captured iteration (the index
-    lives on the device; the kernel zero-fills the frame and raises the bank's status word).  The end of an epoch -- after the
+    """'raw_u8' and 'resident' wire formats: a size index outside the coefficient bank, or a byte offset outside the resident store,
+    cannot be reported by the captured iteration (they live on the device; the kernel zero-fills the frame and raises the bank's
+    status word).  The end of an epoch -- after the
     validation hooks, which expand their batches the same way -- reads the word back and raises.  Nothing to read without a bank."""
 
     def after_train_epoch(self, runner):
@@ -238,8 +239,13 @@ class RawWireStatusHook(Hook):
 
 
 def _finish_runner(runner, cfg, data_loaders):
-    if (cfg.get("data", None) or {}).get("wire", "float32") == "raw_u8":
+    data_cfg = cfg.get("data", None) or {}
+    if data_cfg.get("wire", "float32") in ("raw_u8", "resident"):
         runner.register_hook(RawWireStatusHook(), priority="LOWEST")
+    if data_cfg.get("wire", "float32") == "resident":
+        # the frames move into device memory now, before the first (eager) iteration: a store cannot be loaded during the capture
+        from tripled_amd import resident
+        resident.get_store(data_cfg["store"], _device(), data_cfg.get("resident_reserve_gb", None))
     data_loaders = _maybe_prefetch(data_loaders, cfg)
     if cfg.resume_from:
         runner.resume(cfg.resume_from)

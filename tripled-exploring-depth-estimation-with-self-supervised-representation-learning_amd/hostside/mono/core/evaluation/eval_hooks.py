@@ -64,10 +64,10 @@ def _predict_one(model, sample):
     batch = {}
     for k, v in sample.items():
         t = torch.as_tensor(v)
-        if k == "raw_spec":                              # 'raw_u8' wire format: read by the host in the expansion
+        if k in ("raw_spec", "res_bytes"):               # raw_wire.HOST_KEYS: read by the host in the expansion
             batch[k] = t.unsqueeze(0)
             continue
-        if k == "raw_meta" or (isinstance(k, tuple) and k and k[0] == "raw_u8"):
+        if k == "raw_meta" or (isinstance(k, tuple) and k and k[0] in ("raw_u8", "res_off")):
             batch[k] = t.unsqueeze(0).to(dev)            # bytes / int32; resized by the HIP kernel (no host path: a CPU model raises)
             continue
         if isinstance(k, tuple) and k and k[0] == "color_u8":

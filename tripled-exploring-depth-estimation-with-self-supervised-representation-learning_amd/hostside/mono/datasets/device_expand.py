@@ -13,7 +13,13 @@ runs inside the captured training graph (the bank itself is built in the eager w
 Two limits follow.  "raw_spec" is a host value, so a captured graph bakes in the bank found at capture time: replays do not run this
 function and keep that bank whatever later batches carry, i.e. one run has one (H, W, raw_sizes).  And "raw_meta" is a device value
 the host never reads here: a size index outside the bank zero-fills the frame and raises the bank's status word, which the trainer
-reads at the end of an epoch and DepthEvaluator after its copy to the host (tripled_amd.resize.check_banks); other callers poll it."""
+reads at the end of an epoch and DepthEvaluator after its copy to the host (tripled_amd.resize.check_banks); other callers poll it.
+
+"resident": the loader ships ("res_off", f) int64 [B] -- byte offsets into the store of decoded frames that already lives in device
+memory (tripled_amd.resident) -- with "raw_meta", "raw_spec" and the host key "res_bytes".  The same resize runs, fetching its source rows
+from the store (td_lanczos_resize_u8_indexed).  The store is found by a host lookup (resident.active_store) and its pointer is static;
+the offsets are device values read by the kernel alone, so a captured iteration resizes, on every replay, the frames that replay's
+static input buffers name.  An offset outside the store zero-fills the frame and raises the same status word."""
 import torch
 
 from .raw_wire import parse_spec
@@ -31,28 +37,54 @@ def has_raw_frames(data):
     return isinstance(data, dict) and any(isinstance(k, tuple) and k and k[0] == "raw_u8" for k in data)
 
 
+def has_resident_frames(data):
+    return isinstance(data, dict) and any(isinstance(k, tuple) and k and k[0] == "res_off" for k in data)
+
+
+def _bank_of(data, device):
+    """The coefficient bank "raw_spec" names -- host values only."""
+    from tripled_amd import resize
+    spec = data["raw_spec"]                                                  # a host tensor: no synchronisation
+    if spec.is_cuda or spec.dim() != 2 or not bool((spec == spec[0]).all()):
+        raise ValueError("'raw_spec' must stay on the host and be one configuration per batch: samples of datasets with different "
+                         "sizes or raw_sizes cannot share a batch")
+    height, width, sizes = parse_spec(spec[0])
+    return resize.get_bank(sizes, height, width, device)
+
+
 def expand_device_batch(data):
-    """In place: replaces the ("color_u8", f) or ("raw_u8", f) / "raw_meta" / "raw_spec" entries, and "aug", of a device-resident
-    batch dict."""
-    raw = has_raw_frames(data)
-    if not raw and not has_uint8_frames(data):
+    """In place: replaces the ("color_u8", f), ("raw_u8", f) or ("res_off", f) entries with "raw_meta" / "raw_spec" / "res_bytes", and
+    "aug", of a device-resident batch dict."""
+    raw, res = has_raw_frames(data), has_resident_frames(data)
+    if not raw and not res and not has_uint8_frames(data):
         return data
     from tripled_amd import native, ops
-    frames = _frame_keys(data, "raw_u8" if raw else "color_u8")
+    tag = "res_off" if res else ("raw_u8" if raw else "color_u8")
+    frames = _frame_keys(data, tag)
     first = data[frames[0]]
     if not first.is_cuda:
         raise native.NativeLibraryError("the %s wire format is expanded by a HIP kernel: move the batch to the device first "
-                                        "(or load with wire='float32')" % ("raw_u8" if raw else "uint8"))
+                                        "(or load with wire='float32')" % {"res_off": "resident", "color_u8": "uint8"}.get(tag, tag))
     B = first.shape[0]
-    stacked = torch.cat([data[k] for k in frames], 0)                       # [F*B,3,H,W] uint8 (raw: [F*B,3,Hc,Wc])
+    if res:
+        from tripled_amd import resident
+        if first.dtype != torch.int64:
+            raise ValueError("('res_off', f) must reach the device as int64 (got %s): a float cast loses byte offsets above 2^24" % first.dtype)
+        bank = _bank_of(data, first.device)
+        store = resident.active_store(first.device)                         # registered by resident.get_store: a host lookup
+        want = data["res_bytes"]
+        if want.is_cuda or not bool((want == store.nbytes).all()):
+            raise ValueError("'res_bytes' must stay on the host and name the store loaded on %s (%s, %d bytes): the dataset read another "
+                             "index" % (first.device, store.directory, store.nbytes))
+        offsets = torch.cat([data[k].reshape(-1) for k in frames], 0)       # [F*B] int64 (inside a graph: from the static buffers)
+        meta = data["raw_meta"].to(torch.int32).repeat(len(frames), 1)
+        stacked = resident.resize_from_store_hip(store, offsets, meta, bank)
+        del data["raw_meta"], data["raw_spec"], data["res_bytes"]
+    else:
+        stacked = torch.cat([data[k] for k in frames], 0)                   # [F*B,3,H,W] uint8 (raw: [F*B,3,Hc,Wc])
     if raw:
         from tripled_amd import resize
-        spec = data["raw_spec"]                                              # a host tensor: no synchronisation
-        if spec.is_cuda or spec.dim() != 2 or not bool((spec == spec[0]).all()):
-            raise ValueError("'raw_spec' must stay on the host and be one configuration per batch: samples of datasets with different "
-                             "sizes or raw_sizes cannot share a batch")
-        height, width, sizes = parse_spec(spec[0])
-        bank = resize.get_bank(sizes, height, width, first.device)
+        bank = _bank_of(data, first.device)
         meta = data["raw_meta"].to(torch.int32).repeat(len(frames), 1)       # the frames of a sample share size and flip
         stacked = resize.lanczos_resize_hip(stacked, meta, bank)
         del data["raw_meta"], data["raw_spec"]

@@ -95,6 +95,7 @@ class MonoDataset(Dataset):
         self.flag = np.zeros(len(self), dtype=np.int64)        # single aspect-ratio group for the samplers
         self.gt_depths = None
         self._raw = None
+        self._store_index = None
         if not is_train and gt_depth_path is not None and os.path.exists(str(gt_depth_path)):
             # the reference loads this archive with allow_pickle=True; object arrays are refused here
             self.gt_depths = np.load(gt_depth_path, allow_pickle=False)["data"]
@@ -114,6 +115,23 @@ class MonoDataset(Dataset):
             sizes = raw_wire_mod.raw_sizes_of(self.cfg)
             self._raw = (sizes, raw_wire_mod.canvas_of(sizes), raw_wire_mod.raw_spec(self.height, self.width, sizes))
         return self._raw
+
+    def _resident_index(self):
+        """The index of cfg.data.store ('resident' wire), read once per process and checked against this dataset's configuration."""
+        if self._store_index is None:
+            from tripled_amd import resident
+            store = self.cfg.get("store", None)
+            if not store:
+                raise ValueError("cfg.data.wire = 'resident' needs cfg.data.store, the directory tools/pack_frames.py wrote")
+            index = resident.load_index(store)
+            index.check_config(self.img_ext, self._raw_layout()[0])
+            self._store_index = index
+        return self._store_index
+
+    def _resident_frame(self, index, folder, frame_index, side):
+        """(byte offset, h, w) of a frame in the store, or None when the packer did not find the file."""
+        from tripled_amd import resident
+        return index.frames.get(resident.relative_path(self, folder, frame_index, side))
 
     def postprocess(self, inputs):
         """Hook for subclasses (in-painting masks)."""
@@ -143,14 +161,33 @@ class MonoDataset(Dataset):
         # wire = "raw_u8": the frames travel at their native size; the flip and the LANCZOS resize run on the device too
         # (mono.datasets.raw_wire / csrc/td_resize.hip), with the same draws in the same order
         wire = self.cfg.get("wire", "float32")
-        raw_wire = wire == "raw_u8"
+        # wire = "resident": as "raw_u8", but the decoded frames already live in device memory (tripled_amd.resident): no file is
+        # opened, a frame travels as its byte offset in the store
+        res_wire = wire == "resident"
+        raw_wire = wire == "raw_u8" or res_wire
         u8_wire = wire == "uint8" or raw_wire
         if u8_wire:
             inputs["aug"] = jitter.as_row() if jitter is not None else torch.zeros(9)
         load_flipped = do_flip and not raw_wire
         raw_index = None
         sizes, canvas, spec = self._raw_layout() if raw_wire else (None, None, None)
+        store_index = self._resident_index() if res_wire else None
         for i in self.frame_idxs:
+            if res_wire:
+                other = {"r": "l", "l": "r"}[side] if i == "s" else side
+                entry = self._resident_frame(store_index, folder, frame_index + (0 if i == "s" else i), other)
+                if entry is None and i != "s":                   # sequence boundary: repeat the centre frame
+                    entry = self._resident_frame(store_index, folder, frame_index, side)
+                if entry is None:
+                    raise ValueError("%s does not list %s (sample %d): pack the store from the split lists this dataset reads"
+                                     % (store_index.path, self.get_image_path(folder, frame_index, other), index))
+                idx = raw_wire_mod.size_index(entry[1], entry[2], sizes)
+                if raw_index is not None and idx != raw_index:
+                    raise ValueError("the frames of sample %d have different sizes in %s: 'raw_meta' is one size index per sample"
+                                     % (index, store_index.path))
+                raw_index = idx
+                inputs[("res_off", i)] = torch.tensor(entry[0], dtype=torch.int64)
+                continue
             if i == "s":
                 img = self.get_color(folder, frame_index, {"r": "l", "l": "r"}[side], load_flipped)
             else:
@@ -174,6 +211,8 @@ class MonoDataset(Dataset):
         if raw_wire:
             inputs["raw_meta"] = torch.tensor([raw_index, int(do_flip)], dtype=torch.int32)
             inputs["raw_spec"] = spec.clone()
+        if res_wire:
+            inputs["res_bytes"] = torch.tensor([store_index.total_bytes], dtype=torch.int64)
         K = self.K.copy()
         K[0, :] *= self.width
         K[1, :] *= self.height
@@ -215,7 +254,7 @@ class KITTIInpaintDataset(KITTIDataset):
     erase_count == 1), reference kitti_dataset.py:167-182."""
 
     def postprocess(self, inputs):
-        if ("raw_u8", 0) in inputs:                 # 'raw_u8' wire: the frame is still a canvas; the mask has the network size
+        if ("raw_u8", 0) in inputs or ("res_off", 0) in inputs:     # 'raw_u8' / 'resident' wire: no frame of the network size yet
             shape = (3, self.height, self.width)
         else:
             shape = tuple((inputs[("color", 0, 0)] if ("color", 0, 0) in inputs else inputs[("color_u8", 0)]).shape)

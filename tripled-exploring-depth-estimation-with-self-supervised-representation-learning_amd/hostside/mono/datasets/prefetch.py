@@ -6,7 +6,7 @@ handed over already on the device (float32; uint8 frames of the 'uint8' wire for
 ``mono.datasets.device_expand`` in batch_processor), so ``change_input_variable`` finds nothing left to copy."""
 import torch
 
-from .raw_wire import HOST_KEYS, is_byte_frame
+from .raw_wire import HOST_KEYS, keeps_dtype
 
 
 class DevicePrefetcher:
@@ -29,8 +29,9 @@ class DevicePrefetcher:
                     if not v.is_pinned():
                         v = v.pin_memory()
                     v = v.to(self.device, non_blocking=True)
-                    # the byte wire formats stay bytes (and "raw_meta" int32) until the device-side expansion (device_expand.py)
-                    out[k] = v if (is_byte_frame(k) or k == "raw_meta") else v.float()
+                    # the byte wire formats stay bytes ("raw_meta" int32, the 'resident' wire's offsets int64) until the device-side
+                    # expansion (device_expand.py)
+                    out[k] = v if keeps_dtype(k) else v.float()
                 else:
                     out[k] = v
         return out

@@ -11,17 +11,30 @@ A sample ships
                                   configuration per sample so that a batch describes itself; the expansion requires all rows of a
                                   batch to be equal, and a captured graph keeps the bank of the batch it was captured on
   "aug"          float [9]        as the 'uint8' wire
+
+The 'resident' wire (cfg.data.wire = "resident", tripled_amd.resident) ships, instead of the canvases,
+  ("res_off", f) int64 []         the byte offset of the frame in the store resident on the device; int64 through every staging step
+  "res_bytes"    int64 [1]        the store's length by the index the dataset read: a HOST key like "raw_spec"; the expansion compares it
+                                  with the store loaded on the device
+and "raw_meta", "raw_spec", "aug" unchanged.
 """
 import numpy as np
 import torch
 
 KITTI_RAW_SIZES = ((375, 1242), (370, 1224), (370, 1226), (374, 1238), (376, 1241))
 BYTE_FRAMES = ("color_u8", "raw_u8")     # tuple keys whose tensors stay uint8 until the device-side expansion
-HOST_KEYS = ("raw_spec",)                # entries that are never moved to the device
+HOST_KEYS = ("raw_spec", "res_bytes")    # entries that are never moved to the device
+OFFSET_FRAMES = ("res_off",)             # tuple keys whose tensors stay int64: byte offsets into the resident store ('resident' wire)
 
 
 def is_byte_frame(key):
     return isinstance(key, tuple) and bool(key) and key[0] in BYTE_FRAMES
+
+
+def keeps_dtype(key):
+    """Entries every staging step moves to the device as they are -- bytes, int32 "raw_meta", int64 offsets (a float32 cast would
+    lose the bits of an offset above 2^24) -- until the device-side expansion consumes them."""
+    return key == "raw_meta" or is_byte_frame(key) or (isinstance(key, tuple) and bool(key) and key[0] in OFFSET_FRAMES)
 
 
 def raw_sizes_of(cfg):

@@ -120,6 +120,8 @@ SIGNATURES = {
     "td_odom_snippet_ate": (_I, [_P, _I, _P, _I, _I, _P, _P]),
     "td_odom_sequence_errors": (_I, [_P, _P, _I, ctypes.POINTER(ctypes.c_double), _I, _I, _I, _P, _P, _P, _P, _P]),
     "td_lanczos_resize_u8": (_I, [_P, _P, _IARR, _P, ctypes.c_longlong, _IARR, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "td_lanczos_resize_u8_indexed": (_I, [_P, ctypes.c_longlong, _P, _LLARR, _P, _IARR, _P, ctypes.c_longlong, _IARR, _I, _I, _I, _I, _P,
+                                          _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}

@@ -129,7 +129,8 @@ class LanczosBank:
     tables   int32 device buffer: per size the horizontal coefficients TRANSPOSED [ksx, out_w] (lanes of a wave read consecutive
              columns), horizontal bounds [out_w, 2], vertical coefficients [out_h, ksy], vertical bounds [out_h, 2]
     desc     host int32 [n_sizes, 8]: h, w, ksx, ksy and the four offsets (in ints) into ``tables``
-    status   int32 [1] on the device, 0 until a launch meets a size index outside the bank (``bad_index_seen``)
+    status   int32 [1] on the device, 0 until a launch meets a size index outside the bank (``bad_index_seen``), tables of other
+             sizes, or -- td_lanczos_resize_u8_indexed -- a byte offset outside the resident store
     """
 
     def __init__(self, sizes, out_h, out_w, device):
@@ -168,6 +169,11 @@ class LanczosBank:
         """RuntimeError if a launch met a size index outside the bank since the last check; the status word is cleared, so the
         next check reports new launches only.  Synchronises like ``bad_index_seen``."""
         code = int(self.status.item())
+        if code == 3:
+            self.status.zero_()
+            raise RuntimeError("td_lanczos_resize_u8_indexed zero-filled at least one frame: a byte offset outside the resident store for "
+                               "the bank of %r -> %dx%d (the loader's 'res_off' and the store on the device disagree)"
+                               % (list(self.sizes), self.out_h, self.out_w))
         if code:
             self.status.zero_()
             raise RuntimeError("td_lanczos_resize_u8 zero-filled at least one frame: %s for the bank of %r -> %dx%d (cfg.data.raw_sizes "
@@ -193,7 +199,8 @@ def get_bank(sizes, out_h, out_w, device):
 def check_banks():
     """``raise_if_bad_index`` of every cached bank.  The per-batch call cannot report a bad device-side size index (it would have
     to synchronise), so the consumers of the 'raw_u8' wire call this where they synchronise anyway: the trainer at the end of an
-    epoch, DepthEvaluator after its one copy to the host.  Without a cached bank it does nothing."""
+    epoch, DepthEvaluator after its one copy to the host.  The 'resident' wire's bad byte offsets arrive in the same word and
+    are polled here too.  Without a cached bank it does nothing."""
     for bank in list(_BANKS.values()):
         bank.raise_if_bad_index()
 
