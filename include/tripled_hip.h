@@ -729,6 +729,53 @@ int td_lanczos_resize_u8_indexed(const uint8_t* store, long long store_bytes, co
                                  const int* meta, const int* meta_host, const int* tables, long long table_ints, const int* desc,
                                  int n_sizes, int N, int H, int W, uint8_t* dst, int* status, td_stream_t stream);
 
+/*
+ * Fusion of depth maps and camera poses into a voxel-averaged coloured point cloud (csrc/td_cloud.hip, tripled_amd/cloud.py).
+ * Store, sort, then sum per destination: td_cloud_keys stores a (key, payload) pair per pixel, the caller sorts the keys
+ * (torch.sort), td_cloud_heads marks where a voxel's run starts (the caller's torch.cumsum of the marks numbers the runs),
+ * td_cloud_reduce_* sums every run into its voxel's row and td_cloud_finish turns rows into points.  Everything accumulated is an
+ * integer: results are bit-identical from run to run and do not depend on how a sequence is cut into batches.  No kernel waits
+ * on another workgroup.  An empty input (B, N or V = 0) is a successful no-op without a launch.  Offsets are 64-bit.
+ *
+ * td_cloud_keys.  depth [B,H,W] float32;  color [B,3,H,W] uint8 (planar);  poses [B,3,4] float64, camera-to-world (device);
+ *   inv_K: HOST array, the nine float64 entries of the 3x3 block;  inv_voxel = 1 / voxel, computed once by the caller.
+ *   float64 throughout, every product and sum rounded on its own (pixel (u, v) at integer coordinates, no half-pixel offset):
+ *     ray_k = (m_k0 u + m_k1 v) + m_k2;  p = (depth depth_scale) ray;  world_k = ((r_k0 p_x + r_k1 p_y) + r_k2 p_z) + pose_scale t_k;
+ *     g = world inv_voxel;  i = floor(g);  q = min(1023, (int)floor((g - i) 1024.0))
+ *   a pixel is invalid, by the first cause that holds: (1) x or y is no multiple of stride; (2) it lies within border pixels of
+ *   an image edge; (3) its depth is not finite or depth depth_scale is outside [min_depth, max_range]; (4) edge > 0 and for a
+ *   4-neighbour inside the image the neighbour is not finite or |d - d_nb| > edge min(d, d_nb) (float32, unscaled); (5) a voxel
+ *   coordinate is outside [-2^20, 2^20), or the key would equal the sentinel (the one voxel with all three coordinates 2^20 - 1)
+ *   key [B H W] int64 (out): ((ix + 2^20) << 42) | ((iy + 2^20) << 21) | (iz + 2^20); INT64_MAX for an invalid pixel
+ *   payload [B H W] uint64 (out): qx | qy << 10 | qz << 20 | r << 30 | g << 38 | b << 46; 0 for an invalid pixel
+ *   stats [6] int64 (device) or NULL: incremented by the numbers of valid pixels and of pixels invalid by causes 1 ... 5
+ *   A thread owns 4, 2 or 1 consecutive columns of a row: the widest that divides W and that the base pointers are aligned for.
+ *
+ * td_cloud_heads.  keys [N] int64, sorted ascending;  flags [N] int32 (out): 1 where the key is valid and differs from its
+ *   predecessor.  seg = the inclusive cumulative sum of flags (int64): element i belongs to row seg[i] - 1, and seg[N-1] = V.
+ *
+ * td_cloud_reduce_packed / td_cloud_reduce_rows.  keys, seg [N] as above;  perm [N] int64 or NULL (identity): the source index of
+ *   sorted element i (the sort's permutation; the gather is part of the kernel);  payload [n_src] uint64 as td_cloud_keys wrote it
+ *   (one point per element: count 1), or rows [n_src,7] int64 already-summed rows;  out_keys [V] int64 (out): the key of every
+ *   row;  sums [V,7] int64, ZERO-INITIALISED by the caller (out): count, sum qx, sum qy, sum qz, sum r, sum g, sum b.
+ *   A wave reduces the runs inside its own stretch of 512 elements in registers; a run wholly inside the stretch is written with
+ *   plain stores, the first and last run of a stretch, which may continue in a neighbour's, with 64-bit integer atomics.
+ *   Elements whose seg is outside 1 ... V or whose source index is outside [0, n_src) write and read nothing.
+ *
+ * td_cloud_finish.  keys [V], sums [V,7] -> xyz [V,3] float32 = (float)(((double)i + ((double)sum_q / (double)count + 0.5) / 1024.0)
+ *   voxel);  rgb [V,3] uint8 = (2 sum_c + count) / (2 count), integer;  count [V] int32, saturating;  keep [V] uint8 = count >= min_count.
+ */
+int td_cloud_keys(const float* depth, const uint8_t* color, const double* poses, const double* inv_K, int B, int H, int W,
+                  double depth_scale, double pose_scale, double inv_voxel, int stride, int border, double min_depth, double max_range,
+                  float edge, long long* key, unsigned long long* payload, long long* stats, td_stream_t stream);
+int td_cloud_heads(const long long* keys, long long N, int* flags, td_stream_t stream);
+int td_cloud_reduce_packed(const long long* keys, const long long* seg, const long long* perm, const unsigned long long* payload,
+                           long long n_src, long long N, long long V, long long* out_keys, long long* sums, td_stream_t stream);
+int td_cloud_reduce_rows(const long long* keys, const long long* seg, const long long* perm, const long long* rows, long long n_src,
+                         long long N, long long V, long long* out_keys, long long* sums, td_stream_t stream);
+int td_cloud_finish(const long long* keys, const long long* sums, long long V, double voxel, long long min_count, float* xyz,
+                    uint8_t* rgb, int* count, uint8_t* keep, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Scene reconstruction from a checkpoint: the predicted depth maps and camera poses of a KITTI odometry sequence fused into one
+voxel-averaged coloured point cloud (binary PLY: x y z float, red green blue uchar, count int).  The reference has no such program.
+
+  python scripts/reconstruct.py --config config/cfg_kitti_tripleD.py --checkpoint work/epoch_20.pth --data_path /data/kitti_odom \
+         --sequence 9 [--frames A:B] [--poses FILE] [--voxel V] [--stride S] [--border P] [--max_range R] [--edge E] [--min_count N] \
+         [--depth_scale S] [--pose_scale S] [--batch_size 12] [--precision bf16] [--post_process] [--device cpu] --out cloud.ply
+
+Frames: <data_path>/sequences/NN/image_0/%06d.png; the frame count is the line count of <data_path>/poses/NN.txt (or of --poses).
+Without --poses the model's own poses are used (depth and pose share the model's scale); --poses FILE takes camera-to-world poses
+in KITTI pose text (the ground truth: give --depth_scale, the model's unit in metres, ~36 for a stereo-trained checkpoint).
+--voxel, --max_range and --edge are in the model's units; their defaults are untuned starting values.  The work is
+tripled_amd.cloud.SceneFuser (csrc/td_cloud.hip on a HIP device); the last line printed is the statistics.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import tripled_amd  # noqa: F401,E402
+from mmcv import Config  # noqa: E402
+from mono.datasets.kitti_dataset import KITTIOdomDataset, odom_sequence_files  # noqa: E402
+from mono.model import MONO  # noqa: E402
+from tripled_amd import cloud, odometry  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--data_path", required=True, help="KITTI odometry root (sequences/, poses/)")
+    ap.add_argument("--sequence", type=int, default=9)
+    ap.add_argument("--frames", default=None, help="A:B, the frames A ... B-1 of the sequence (default: all)")
+    ap.add_argument("--poses", default=None, help="camera-to-world poses in KITTI pose text instead of the model's own")
+    ap.add_argument("--height", type=int, default=None, help="default: the config's")
+    ap.add_argument("--width", type=int, default=None)
+    ap.add_argument("--img_ext", default=".png")
+    ap.add_argument("--voxel", type=float, default=cloud.DEFAULT_VOXEL)
+    ap.add_argument("--stride", type=int, default=1)
+    ap.add_argument("--border", type=int, default=0)
+    ap.add_argument("--min_depth", type=float, default=cloud.DEFAULT_MIN_DEPTH)
+    ap.add_argument("--max_range", type=float, default=cloud.DEFAULT_MAX_RANGE)
+    ap.add_argument("--edge", type=float, default=cloud.DEFAULT_EDGE)
+    ap.add_argument("--min_count", type=int, default=1)
+    ap.add_argument("--depth_scale", type=float, default=1.0)
+    ap.add_argument("--pose_scale", type=float, default=1.0)
+    ap.add_argument("--batch_size", type=int, default=12)
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--post_process", action="store_true")
+    ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--out", required=True)
+    args = ap.parse_args()
+    cfg = Config.fromfile(args.config)
+    cfg.model["imgs_per_gpu"] = 1
+    height, width = args.height or cfg.model["height"], args.width or cfg.model["width"]
+    model = MONO.module_dict[cfg.model["name"]](cfg.model)
+    ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True)      # executes nothing from the file
+    model.load_state_dict(ckpt["state_dict"], strict=True)
+    model.eval().to(args.device)
+    poses = odometry.load_kitti_poses(args.poses) if args.poses else None
+    n_frames = len(poses) if poses is not None else len(odometry.load_kitti_poses(
+        os.path.join(args.data_path, "poses", "%02d.txt" % args.sequence)))
+    frames = None
+    if args.frames:
+        a, _, b = args.frames.partition(":")
+        frames = (int(a or 0), int(b or n_frames))
+    dataset = KITTIOdomDataset(args.data_path, odom_sequence_files(args.sequence, n_frames), height, width, [0, 1], is_train=False,
+                               img_ext=args.img_ext)
+    fuser = cloud.SceneFuser(model, height, width, args.device, voxel=args.voxel, batch_size=args.batch_size, precision=args.precision,
+                             stride=args.stride, border=args.border, min_depth=args.min_depth, max_range=args.max_range, edge=args.edge,
+                             min_count=args.min_count, depth_scale=args.depth_scale, pose_scale=args.pose_scale,
+                             post_process=args.post_process)
+    print("-> Fusing sequence %02d: frames %s of %d" % (args.sequence, "%d:%d" % frames if frames else "0:%d" % n_frames, n_frames))
+    result = fuser.fuse(dataset, poses=poses, frames=frames)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    cloud.save_ply(args.out, result.xyz, result.rgb, result.count)
+    print("saved %d points to %s" % (len(result.keys), args.out))
+    print(" ".join("%s %d" % (k, v) for k, v in result.stats.items()))
+
+
+if __name__ == "__main__":
+    main()

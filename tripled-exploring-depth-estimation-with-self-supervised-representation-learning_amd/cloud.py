@@ -1,0 +1,524 @@
+"""Scene reconstruction: the predicted depth maps and camera poses of a sequence fused into one voxel-averaged coloured point cloud.
+
+The model is a joint depth-and-pose network: its depth maps and its poses share one scale, so back-projecting every frame through
+its own pose gives the scene's geometry.  A raw cloud grows with the number of frames (KITTI sequence 09 at 192 x 640 is 195 million
+points); a voxel-fused one is bounded by the scene.  The reference has no such program (its only 3-D picture is draw_odometry.py's
+bird's-eye trajectory).
+
+The design is store, sort, then sum per destination (csrc/td_cloud.hip): a kernel stores a (voxel key, packed payload) pair per
+pixel, torch.sort orders the keys, a kernel marks where a voxel's run starts, torch.cumsum numbers the runs and a segmented-sum
+kernel adds every run into its voxel's row.  Everything that is accumulated is an integer (a count, 10-bit positions inside the
+voxel, 8-bit colours), so the cloud is bit-identical from run to run, does not depend on how the sequence is cut into batches, and
+equals the numpy statement below exactly.
+
+Three layers, as in odometry.py:
+  * host statements in numpy (``keys_numpy``, ``voxel_table_numpy``, ``finish_numpy``, ``fuse_numpy``, ``pack_key`` / ``unpack_key``,
+    ``save_ply`` / ``load_ply``): the host path (``device='cpu'``) and what the kernels are tested against.  The arithmetic is written
+    element-wise in the kernel's operation order: no ``@`` and no einsum, which BLAS may fuse;
+  * ``keys_hip``, ``heads_hip``, ``reduce_hip``, ``finish_hip``, ``merge_hip`` (and ``table_hip`` / ``fuse_hip``, which chain them):
+    device tensors only, a CPU tensor is an error; the kernels themselves never synchronise;
+  * ``SceneFuser``: frames of a dataset -> DepthPredictor + OdometryEvaluator.relative_poses / trajectory_hip -> the cloud.
+
+The exact arithmetic (float64; every product and sum rounded on its own; pixel (u, v) at integer coordinates like the reference's
+Backproject, no half-pixel offset):
+    ray_k   = (m_k0 u + m_k1 v) + m_k2                       m = the 3x3 block of inv_K
+    p       = (depth depth_scale) ray
+    world_k = ((r_k0 p_x + r_k1 p_y) + r_k2 p_z) + pose_scale t_k      [r | t] = the frame's camera-to-world pose
+    g = world inv_voxel;  i = floor(g);  q = min(1023, int(floor((g - i) 1024.0)))
+    key = ((i_x + 2^20) << 42) | ((i_y + 2^20) << 21) | (i_z + 2^20);  payload = q_x | q_y << 10 | q_z << 20 | r << 30 | g << 38 | b << 46
+    voxel:  xyz = float32((i + (sum q / count + 0.5) / 1024.0) voxel);  rgb = (2 sum c + count) // (2 count)
+"""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import infer, native, odometry
+
+HALF = 1 << 20                       # voxel coordinates lie in [-2^20, 2^20)
+INVALID_KEY = (1 << 63) - 1          # csrc/td_cloud.hip: TD_CLOUD_INVALID; the sort puts it last
+CAUSES = ("valid", "invalid_stride", "invalid_border", "invalid_depth", "invalid_edge", "invalid_range")
+
+# Starting values in the MODEL's units: the stereo baseline (0.54 m) is 0.015 of them and the evaluation multiplies depths by 36, so
+# one unit is about 36 m for a stereo-trained checkpoint.  UNTUNED: nobody has looked at a cloud of a trained checkpoint with them.
+DEFAULT_VOXEL = 0.005        # ~0.18 m
+DEFAULT_MIN_DEPTH = 0.1      # the depth network's own lower limit (disp_to_depth)
+DEFAULT_MAX_RANGE = 1.0      # ~36 m: monocular depth degrades with range
+DEFAULT_EDGE = 0.1           # 10 % depth step to a 4-neighbour
+
+Cloud = collections.namedtuple("Cloud", "xyz rgb count keys stats")
+Cloud.__doc__ = """xyz float32 [V,3], rgb uint8 [V,3], count int32 [V] (points fused into the voxel, saturating), keys int64 [V] (ascending:
+the output order is defined), on the fuser's device (numpy arrays on the host path);  stats: dict of Python ints: points (pixels
+seen), valid, invalid_stride / _border / _depth / _edge / _range (by the first cause that holds), voxels (before min_count),
+voxels_dropped (by min_count)."""
+
+PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("count", "<i4")])
+_PLY_TYPES = {"float": "<f4", "float32": "<f4", "uchar": "u1", "uint8": "u1", "int": "<i4", "int32": "<i4"}
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# host statements
+
+def pack_key(ix, iy, iz):
+    """Voxel coordinates in [-2^20, 2^20) -> int64 key (ascending key order = x major, then y, then z)."""
+    ix, iy, iz = (np.asarray(v, dtype=np.int64) for v in (ix, iy, iz))
+    for v in (ix, iy, iz):
+        if v.size and (v.min() < -HALF or v.max() >= HALF):
+            raise ValueError("voxel coordinates: [-2^20, 2^20)")
+    return ((ix + HALF) << 42) | ((iy + HALF) << 21) | (iz + HALF)
+
+
+def unpack_key(key):
+    """int64 keys -> (ix, iy, iz) int64."""
+    key = np.asarray(key, dtype=np.int64)
+    mask = 2 * HALF - 1
+    return ((key >> 42) & mask) - HALF, ((key >> 21) & mask) - HALF, (key & mask) - HALF
+
+
+def unpack_payload(payload):
+    """uint64 payloads [n] -> int64 rows [n,7]: 1, qx, qy, qz, r, g, b."""
+    p = np.asarray(payload).astype(np.uint64)
+    cols = [np.ones(p.shape, np.uint64), p & np.uint64(1023), (p >> np.uint64(10)) & np.uint64(1023), (p >> np.uint64(20)) & np.uint64(1023),
+            (p >> np.uint64(30)) & np.uint64(255), (p >> np.uint64(38)) & np.uint64(255), (p >> np.uint64(46)) & np.uint64(255)]
+    return np.stack(cols, -1).astype(np.int64).reshape(-1, 7)
+
+
+def _check_params(voxel, stride, border, min_depth, max_range, edge, min_count=1):
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError("voxel: a positive size, got %r" % (voxel,))
+    if int(stride) < 1 or int(border) < 0 or int(min_count) < 1:
+        raise ValueError("stride >= 1, border >= 0, min_count >= 1; got %r, %r, %r" % (stride, border, min_count))
+    if not (edge >= 0) or not (min_depth <= max_range):
+        raise ValueError("edge >= 0 and min_depth <= max_range; got %r, %r, %r" % (edge, min_depth, max_range))
+
+
+def _inv_K9(inv_K):
+    m = np.asarray(inv_K, dtype=np.float64)
+    if m.shape in ((3, 3), (4, 4)):
+        m = m[:3, :3]
+    m = np.ascontiguousarray(m).reshape(-1)
+    if m.shape != (9,):
+        raise ValueError("inv_K: 3x3 (or 4x4, whose 3x3 block is used), got %s" % (np.shape(inv_K),))
+    return m
+
+
+def camera_points_numpy(depth, inv_K, depth_scale=1.0):
+    """depth float32 [B,H,W] -> float64 [3,B,H,W]: p = (depth depth_scale) ray, ray_k = (m_k0 u + m_k1 v) + m_k2 at integer pixel
+    coordinates (the reference's Backproject, oracle/geometry.py:backproject, in float64)."""
+    d = np.asarray(depth, dtype=np.float32)
+    m = _inv_K9(inv_K)
+    H, W = d.shape[1:]
+    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    with np.errstate(invalid="ignore", over="ignore"):
+        ds = d.astype(np.float64) * np.float64(depth_scale)
+        return np.stack([ds * ((m[3 * k] * u + m[3 * k + 1] * v) + m[3 * k + 2]) for k in range(3)], 0)
+
+
+def keys_numpy(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_voxel=1.0 / DEFAULT_VOXEL, stride=1, border=0,
+               min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=0.0):
+    """depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4] -> (key int64 [B H W], payload uint64 [B H W], counts
+    int64 [6] in the order of CAUSES).  The statement td_cloud_keys is tested against, operation for operation."""
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    c = np.ascontiguousarray(color, dtype=np.uint8)
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    if d.ndim != 3 or c.shape != (d.shape[0], 3) + d.shape[1:] or P.shape != (d.shape[0], 3, 4):
+        raise ValueError("depth [B,H,W], color [B,3,H,W], poses [B,3,4]; got %s, %s, %s" % (d.shape, c.shape, P.shape))
+    m = _inv_K9(inv_K)
+    B, H, W = d.shape
+    stride, border = int(stride), int(border)
+    depth_scale, pose_scale, inv_voxel = np.float64(depth_scale), np.float64(pose_scale), np.float64(inv_voxel)
+    ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    ys, xs = np.broadcast_to(ys, d.shape), np.broadcast_to(xs, d.shape)
+    cause = np.zeros(d.shape, np.int8)
+
+    def mark(mask, code):
+        cause[(cause == 0) & mask] = code
+
+    with np.errstate(invalid="ignore", over="ignore"):
+        ds = d.astype(np.float64) * depth_scale
+        mark((xs % stride != 0) | (ys % stride != 0), 1)
+        mark((xs < border) | (xs >= W - border) | (ys < border) | (ys >= H - border), 2)
+        mark(~np.isfinite(d) | ~((ds >= np.float64(min_depth)) & (ds <= np.float64(max_range))), 3)
+        if edge > 0:
+            e = np.float32(edge)
+            bad = np.zeros(d.shape, bool)
+            for axis, shift in ((1, 1), (1, -1), (2, 1), (2, -1)):
+                nb = np.roll(d, shift, axis=axis)
+                inside = np.ones(d.shape, bool)
+                edge_line = [slice(None)] * 3
+                edge_line[axis] = 0 if shift == 1 else -1
+                inside[tuple(edge_line)] = False           # the rolled-in line is no neighbour
+                bad |= inside & (~np.isfinite(nb) | (np.abs(d - nb) > e * np.minimum(d, nb)))
+            mark(bad, 4)
+        px, py, pz = camera_points_numpy(d, m, depth_scale)
+        g, f = [], []
+        for k in range(3):
+            r0, r1, r2, t = (P[:, k, j].reshape(B, 1, 1) for j in range(4))
+            world = ((r0 * px + r1 * py) + r2 * pz) + pose_scale * t
+            g.append(world * inv_voxel)
+            f.append(np.floor(g[k]))
+        inside = np.ones(d.shape, bool)
+        for k in range(3):
+            inside &= (f[k] >= -float(HALF)) & (f[k] < float(HALF))          # a NaN fails both
+        mark(~inside, 5)
+        ok = cause == 0
+        i = [np.where(ok, f[k], 0.0).astype(np.int64) + HALF for k in range(3)]
+        key = (i[0] << 42) | (i[1] << 21) | i[2]
+        mark(ok & (key == INVALID_KEY), 5)                                   # the one corner voxel whose key is the sentinel
+        ok = cause == 0
+        q = [np.minimum(1023, np.where(ok, np.floor((g[k] - f[k]) * 1024.0), 0.0).astype(np.int64)).astype(np.uint64) for k in range(3)]
+    payload = q[0] | (q[1] << np.uint64(10)) | (q[2] << np.uint64(20))
+    for ch, shift in ((0, 30), (1, 38), (2, 46)):
+        payload = payload | (c[:, ch].astype(np.uint64) << np.uint64(shift))
+    key = np.where(ok, key, INVALID_KEY).astype(np.int64).reshape(-1)
+    payload = np.where(ok, payload, np.uint64(0)).astype(np.uint64).reshape(-1)
+    return key, payload, np.bincount(cause.reshape(-1), minlength=6).astype(np.int64)
+
+
+def voxel_table_numpy(key, rows):
+    """Points (key int64 [n]; rows: uint64 payloads [n] or int64 rows [n,7]) -> (keys int64 [V] ascending, sums int64 [V,7]): sort,
+    np.unique, np.add.reduceat.  Invalid keys are dropped."""
+    key = np.asarray(key, dtype=np.int64).reshape(-1)
+    rows = np.asarray(rows)
+    rows = unpack_payload(rows) if rows.ndim == 1 else rows.astype(np.int64).reshape(-1, 7)
+    if len(rows) != len(key):
+        raise ValueError("one row per key: %d keys, %d rows" % (len(key), len(rows)))
+    valid = key != INVALID_KEY
+    key, rows = key[valid], rows[valid]
+    if not len(key):
+        return np.zeros(0, np.int64), np.zeros((0, 7), np.int64)
+    order = np.argsort(key, kind="stable")
+    key, rows = key[order], rows[order]
+    ukeys, starts = np.unique(key, return_index=True)
+    return ukeys, np.add.reduceat(rows, starts, axis=0)
+
+
+def finish_numpy(keys, sums, voxel, min_count=1):
+    """(keys [V], sums [V,7]) -> (xyz float32 [V,3], rgb uint8 [V,3], count int32 [V], keep bool [V])."""
+    keys, sums = np.asarray(keys, np.int64), np.asarray(sums, np.int64).reshape(-1, 7)
+    n = sums[:, 0]
+    i = np.stack(unpack_key(keys), -1).astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        xyz = ((i + (sums[:, 1:4].astype(np.float64) / n.astype(np.float64)[:, None] + 0.5) / 1024.0) * np.float64(voxel)).astype(np.float32)
+    rgb = ((2 * sums[:, 4:7] + n[:, None]) // np.maximum(2 * n[:, None], 1)).astype(np.uint8)
+    count = np.minimum(n, 0x7fffffff).astype(np.int32)
+    return xyz, rgb, count, n >= int(min_count)
+
+
+def _stats(counts, voxels, kept):
+    out = {"points": int(np.sum(counts))}
+    out.update({name: int(v) for name, v in zip(CAUSES, counts)})
+    out["voxels"], out["voxels_dropped"] = int(voxels), int(voxels) - int(kept)
+    return out
+
+
+def fuse_numpy(depth, color, poses, inv_K, voxel=DEFAULT_VOXEL, stride=1, border=0, min_depth=DEFAULT_MIN_DEPTH,
+               max_range=DEFAULT_MAX_RANGE, edge=0.0, min_count=1, depth_scale=1.0, pose_scale=1.0):
+    """All frames at once -> Cloud of numpy arrays: keys_numpy, voxel_table_numpy, finish_numpy."""
+    _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
+    key, payload, counts = keys_numpy(depth, color, poses, inv_K, depth_scale, pose_scale, 1.0 / float(voxel), stride, border, min_depth,
+                                      max_range, edge)
+    keys, sums = voxel_table_numpy(key, payload)
+    xyz, rgb, count, keep = finish_numpy(keys, sums, voxel, min_count)
+    return Cloud(xyz[keep], rgb[keep], count[keep], keys[keep], _stats(counts, len(keys), int(keep.sum())))
+
+
+def save_ply(path, xyz, rgb, count):
+    """binary_little_endian 1.0 PLY: x y z float, red green blue uchar, count int; one structured array, one write."""
+    xyz, rgb, count = (np.asarray(t.cpu() if torch.is_tensor(t) else t) for t in (xyz, rgb, count))
+    n = len(xyz)
+    if xyz.shape != (n, 3) or rgb.shape != (n, 3) or count.shape != (n,):
+        raise ValueError("xyz [n,3], rgb [n,3], count [n]; got %s, %s, %s" % (xyz.shape, rgb.shape, count.shape))
+    rec = np.empty(n, PLY_DTYPE)
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    rec["count"] = count
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n]
+    header += ["property %s %s" % ({"<f4": "float", "u1": "uchar", "<i4": "int"}[PLY_DTYPE[name].str.replace("|", "")], name)
+               for name in PLY_DTYPE.names]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def load_ply(path):
+    """A binary_little_endian PLY with one vertex element of scalar properties -> structured array (save_ply's: PLY_DTYPE)."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s: not a PLY file" % path)
+        n, fields, fmt = None, [], None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: no end_header" % path)
+            words = line.decode("ascii").split()
+            if words[:1] == ["end_header"]:
+                break
+            if words[:1] == ["format"]:
+                fmt = words[1]
+            elif words[:2] == ["element", "vertex"]:
+                n = int(words[2])
+            elif words[:1] == ["element"]:
+                raise ValueError("%s: only a vertex element is read" % path)
+            elif words[:1] == ["property"]:
+                if len(words) != 3 or words[1] not in _PLY_TYPES:
+                    raise ValueError("%s: unsupported property %r" % (path, " ".join(words)))
+                fields.append((words[2], _PLY_TYPES[words[1]]))
+        if fmt != "binary_little_endian" or n is None:
+            raise ValueError("%s: binary_little_endian with a vertex element expected" % path)
+        dtype = np.dtype(fields)
+        data = f.read()
+    if len(data) != n * dtype.itemsize:
+        raise ValueError("%s: %d bytes of vertices, expected %d" % (path, len(data), n * dtype.itemsize))
+    return np.frombuffer(data, dtype=dtype, count=n).copy()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the kernels
+
+def _device(*tensors):
+    for t in tensors:
+        if not t.is_cuda:
+            raise native.NativeLibraryError("libtripled_hip needs device tensors (got a %s tensor)" % t.device)
+
+
+def _i64(t, name, n=None):
+    _device(t)
+    if t.dtype != torch.int64 or t.dim() != 1 or (n is not None and t.shape[0] != n):
+        raise ValueError("%s: int64 [%s], got %s %s" % (name, "n" if n is None else n, tuple(t.shape), t.dtype))
+    return t.contiguous()
+
+
+def keys_hip(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_voxel=1.0 / DEFAULT_VOXEL, stride=1, border=0,
+             min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=0.0, stats=None):
+    """keys_numpy as one launch of td_cloud_keys -> (key int64 [B H W], payload int64 [B H W]: the uint64's bits).  ``stats``: an int64
+    [6] device tensor that the launch increments (the order of CAUSES), or None."""
+    lib = native.load()
+    _device(depth, color, poses)
+    if depth.dtype != torch.float32 or depth.dim() != 3 or color.dtype != torch.uint8 or \
+            tuple(color.shape) != (depth.shape[0], 3) + tuple(depth.shape[1:]) or poses.dtype != torch.float64 or \
+            tuple(poses.shape) != (depth.shape[0], 3, 4):
+        raise ValueError("depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4]; got %s %s, %s %s, %s %s" % (
+            tuple(depth.shape), depth.dtype, tuple(color.shape), color.dtype, tuple(poses.shape), poses.dtype))
+    if int(stride) < 1 or int(border) < 0 or not inv_voxel > 0 or not edge >= 0:
+        raise ValueError("stride >= 1, border >= 0, inv_voxel > 0, edge >= 0")
+    if stats is not None:
+        stats = _i64(stats, "stats", 6)
+    m = _inv_K9(inv_K)
+    B, H, W = depth.shape
+    key = torch.empty(B * H * W, dtype=torch.int64, device=depth.device)
+    payload = torch.empty(B * H * W, dtype=torch.int64, device=depth.device)
+    if B * H * W == 0:                   # an empty tensor has no pointer to pass
+        return key, payload
+    native.check(lib.td_cloud_keys(native.ptr(depth.contiguous()), native.ptr(color.contiguous()), native.ptr(poses.contiguous()),
+                                   (ctypes.c_double * 9)(*m), B, H, W, float(depth_scale), float(pose_scale), float(inv_voxel),
+                                   int(stride), int(border), float(min_depth), float(max_range), float(edge), native.ptr(key),
+                                   native.ptr(payload), native.ptr(stats), native.stream()), "td_cloud_keys")
+    return key, payload
+
+
+def heads_hip(sorted_keys):
+    """Sorted int64 keys [N] -> int32 [N]: 1 where a valid key differs from its predecessor (td_cloud_heads)."""
+    lib = native.load()
+    keys = _i64(sorted_keys, "sorted_keys")
+    flags = torch.empty(keys.shape[0], dtype=torch.int32, device=keys.device)
+    if keys.shape[0] == 0:
+        return flags
+    native.check(lib.td_cloud_heads(native.ptr(keys), keys.shape[0], native.ptr(flags), native.stream()), "td_cloud_heads")
+    return flags
+
+
+def reduce_hip(sorted_keys, seg, perm, src, V):
+    """The segmented sum -> (keys int64 [V], sums int64 [V,7]).  ``seg``: torch.cumsum(heads_hip(sorted_keys), 0) (int64, inclusive);
+    ``perm``: the sort's permutation or None;  ``src``: int64 [n] payloads as keys_hip wrote them (td_cloud_reduce_packed) or int64
+    [n,7] already-summed rows (td_cloud_reduce_rows);  V = seg[-1], which the caller has read."""
+    lib = native.load()
+    keys = _i64(sorted_keys, "sorted_keys")
+    N, V = keys.shape[0], int(V)
+    seg = _i64(seg, "seg", N)
+    perm = None if perm is None else _i64(perm, "perm", N)
+    _device(src)
+    packed = src.dim() == 1
+    if src.dtype != torch.int64 or not (packed or (src.dim() == 2 and src.shape[1] == 7)):
+        raise ValueError("src: int64 [n] payloads or int64 [n,7] rows, got %s %s" % (tuple(src.shape), src.dtype))
+    if not 0 <= V <= N:
+        raise ValueError("V: 0 ... %d, got %d" % (N, V))
+    out_keys = torch.empty(V, dtype=torch.int64, device=keys.device)
+    sums = torch.zeros(V, 7, dtype=torch.int64, device=keys.device)
+    if V == 0:
+        return out_keys, sums
+    fn, what = (lib.td_cloud_reduce_packed, "td_cloud_reduce_packed") if packed else (lib.td_cloud_reduce_rows, "td_cloud_reduce_rows")
+    native.check(fn(native.ptr(keys), native.ptr(seg), native.ptr(perm), native.ptr(src.contiguous()), src.shape[0], N, V,
+                    native.ptr(out_keys), native.ptr(sums), native.stream()), what)
+    return out_keys, sums
+
+
+def finish_hip(keys, sums, voxel, min_count=1):
+    """finish_numpy as td_cloud_finish -> (xyz float32 [V,3], rgb uint8 [V,3], count int32 [V], keep uint8 [V])."""
+    lib = native.load()
+    keys = _i64(keys, "keys")
+    V = keys.shape[0]
+    _device(sums)
+    if sums.dtype != torch.int64 or tuple(sums.shape) != (V, 7):
+        raise ValueError("sums: int64 [%d,7], got %s %s" % (V, tuple(sums.shape), sums.dtype))
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError("voxel: a positive size, got %r" % (voxel,))
+    dev = keys.device
+    xyz, rgb = torch.empty(V, 3, dtype=torch.float32, device=dev), torch.empty(V, 3, dtype=torch.uint8, device=dev)
+    count, keep = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.uint8, device=dev)
+    if V == 0:
+        return xyz, rgb, count, keep
+    native.check(lib.td_cloud_finish(native.ptr(keys), native.ptr(sums.contiguous()), V, float(voxel), int(min_count), native.ptr(xyz),
+                                     native.ptr(rgb), native.ptr(count), native.ptr(keep), native.stream()), "td_cloud_finish")
+    return xyz, rgb, count, keep
+
+
+def table_hip(key, src):
+    """voxel_table_numpy on the device: torch.sort, heads_hip, torch.cumsum, reduce_hip -> (keys [V] ascending, sums [V,7]).
+    ONE host synchronisation: V = seg[-1] sizes the output."""
+    key = _i64(key, "key")
+    if key.shape[0] == 0:
+        return key.new_zeros(0), key.new_zeros(0, 7)
+    sorted_keys, perm = torch.sort(key)
+    seg = torch.cumsum(heads_hip(sorted_keys), 0)
+    V = int(seg[-1].item())
+    return reduce_hip(sorted_keys, seg, perm, src, V)
+
+
+def merge_hip(keys_a, sums_a, keys_b, sums_b):
+    """Two voxel lists (unique keys, [.,7] rows) -> their union, rows of equal keys added: concatenate, table_hip."""
+    keys_a, keys_b = _i64(keys_a, "keys_a"), _i64(keys_b, "keys_b")
+    _device(sums_a, sums_b)
+    for k, s in ((keys_a, sums_a), (keys_b, sums_b)):
+        if s.dtype != torch.int64 or tuple(s.shape) != (k.shape[0], 7):
+            raise ValueError("sums: int64 [%d,7], got %s %s" % (k.shape[0], tuple(s.shape), s.dtype))
+    if keys_a.shape[0] == 0:
+        return keys_b, sums_b
+    if keys_b.shape[0] == 0:
+        return keys_a, sums_a
+    return table_hip(torch.cat([keys_a, keys_b]), torch.cat([sums_a, sums_b]))
+
+
+class _DeviceMap:
+    """The running voxel map: sorted unique keys and their rows, plus the pixel counters."""
+
+    def __init__(self, device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale):
+        self.args = (inv_K, float(depth_scale), float(pose_scale), 1.0 / float(voxel), stride, border, min_depth, max_range, edge)
+        self.keys = torch.zeros(0, dtype=torch.int64, device=device)
+        self.sums = torch.zeros(0, 7, dtype=torch.int64, device=device)
+        self.counts = torch.zeros(6, dtype=torch.int64, device=device)
+
+    def add(self, depth, color, poses):
+        key, payload = keys_hip(depth, color, poses, *self.args, stats=self.counts)
+        self.keys, self.sums = merge_hip(self.keys, self.sums, *table_hip(key, payload))
+
+    def cloud(self, voxel, min_count):
+        xyz, rgb, count, keep = finish_hip(self.keys, self.sums, voxel, min_count)
+        keep = keep.bool()
+        out = (xyz[keep], rgb[keep], count[keep], self.keys[keep])
+        return Cloud(*out, _stats(self.counts.cpu().numpy(), self.keys.shape[0], out[3].shape[0]))
+
+
+def fuse_hip(depth, color, poses, inv_K, voxel=DEFAULT_VOXEL, batch_size=None, stride=1, border=0, min_depth=DEFAULT_MIN_DEPTH,
+             max_range=DEFAULT_MAX_RANGE, edge=0.0, min_count=1, depth_scale=1.0, pose_scale=1.0):
+    """fuse_numpy on the device, ``batch_size`` frames at a time (default: all at once) -> Cloud of device tensors."""
+    _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
+    _device(depth, color, poses)
+    n = depth.shape[0]
+    step = n if batch_size is None else int(batch_size)
+    if step < 1 and n:
+        raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
+    vmap = _DeviceMap(depth.device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale)
+    for at in range(0, n, max(step, 1)):
+        vmap.add(depth[at:at + step], color[at:at + step], poses[at:at + step])
+    return vmap.cloud(voxel, min_count)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+
+def dataset_inv_K(dataset):
+    """The float64 inverse of the 3x3 block of the dataset's inputs["K"] (pixels at the dataset's frame size)."""
+    K = np.asarray(dataset[0]["K"], dtype=np.float64)
+    return np.linalg.inv(K[:3, :3])
+
+
+class SceneFuser:
+    """fuse(dataset, poses=None, frames=None) -> Cloud.
+
+    model       a model of this build with a depth network and, for ``poses=None``, ``PoseEncoder`` / ``PoseDecoder``; it is never
+                moved or changed (DepthPredictor and OdometryEvaluator work on their own copies where they must)
+    height, width  the depth network's size; the depth maps come back at the dataset's frame size
+    device      'cuda[:i]': the frames are uploaded once as uint8 (odometry.dataset_frames_u8); predicted poses go from
+                OdometryEvaluator.relative_poses through trajectory_hip without visiting the host; per batch of ``batch_size`` frames:
+                DepthPredictor (which wants HWC input: one permuted copy of the batch's frames), keys_hip, torch.sort, heads / cumsum
+                / reduce, merge_hip into the running map, which stays sorted by key.  Memory: one batch of points plus the map.
+                Two host synchronisations per batch (the voxel counts of the batch and of the merged map size their outputs).
+                'cpu': the host statements.
+    voxel, min_depth, max_range  in the MODEL's units (the stereo baseline is 0.015 of them, x 36 gives metres); the defaults of these
+                and of ``edge`` are UNTUNED starting values
+    stride, border   use every stride-th pixel in x and y; drop ``border`` pixels at every image edge
+    edge        flying-pixel filter: a pixel whose depth differs from a 4-neighbour's by more than edge x the smaller one is dropped
+    min_count   drop voxels that fewer points fell into
+    depth_scale, pose_scale  multiply the depths / the pose translations (ground-truth poses in metres: depth_scale = the model's
+                unit in metres, ~36 for the reference's stereo-trained checkpoints)
+    """
+
+    def __init__(self, model, height, width, device, voxel=DEFAULT_VOXEL, batch_size=12, precision="fp32", stride=1, border=0,
+                 min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=DEFAULT_EDGE, min_count=1, depth_scale=1.0,
+                 pose_scale=1.0, post_process=False):
+        _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
+        if int(batch_size) < 1:
+            raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
+        self.device = torch.device(device)
+        self.on_hip = self.device.type == "cuda"
+        self.model = model
+        self.batch_size, self.precision = int(batch_size), precision
+        self.predictor = infer.DepthPredictor(model, height, width, self.device, precision=precision, post_process=post_process)
+        self.voxel, self.min_count = float(voxel), int(min_count)
+        self.params = dict(stride=int(stride), border=int(border), min_depth=float(min_depth), max_range=float(max_range),
+                           edge=float(edge), depth_scale=float(depth_scale), pose_scale=float(pose_scale))
+
+    def _poses(self, dataset, frames, poses):
+        """float64 [n+1,3,4] camera-to-world, on the device (a numpy array on the host path)."""
+        m = frames.shape[0]
+        if poses is not None:
+            p = np.ascontiguousarray(np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, dtype=np.float64))
+            if p.ndim != 3 or p.shape[0] != m or p.shape[1:] not in ((3, 4), (4, 4)):
+                raise ValueError("poses: [%d,3,4] camera-to-world for %d frames, got %s" % (m, m, p.shape))
+            p = np.ascontiguousarray(p[:, :3])
+            return torch.from_numpy(p).to(self.device) if self.on_hip else p
+        rel = odometry.OdometryEvaluator(self.model, self.device, self.batch_size, self.precision).relative_poses(dataset, frames=frames)
+        return odometry.trajectory_hip(rel) if self.on_hip else odometry.trajectory_numpy(rel.numpy())
+
+    def fuse(self, dataset, poses=None, frames=None, debug=None):
+        """``poses``: any [n+1,3,4] camera-to-world array (KITTI ground truth with the user's depth_scale); None: the model's own.
+        ``frames``: (first, last + 1) of the n+1 frames to fuse (poses are still computed from frame 0).  ``debug``: a dict that
+        receives the "depth" maps [m,H,W] and the "poses" [n+1,3,4] that were fused."""
+        host_frames = odometry.dataset_frames_u8(dataset)
+        m = host_frames.shape[0]
+        first, last = (0, m) if frames is None else (int(frames[0]), int(frames[1]))
+        if not 0 <= first < last <= m:
+            raise ValueError("frames: 0 <= first < last <= %d, got %r" % (m, frames))
+        inv_K = dataset_inv_K(dataset)
+        resident = host_frames.to(self.device)                                   # every frame: one upload, as bytes
+        all_poses = self._poses(dataset, resident, poses)
+        depths = []
+        with torch.no_grad():
+            if self.on_hip:
+                vmap = _DeviceMap(self.device, inv_K, self.voxel, **self.params)
+            for at in range(first, last, self.batch_size):
+                color = resident[at:min(at + self.batch_size, last)]
+                depth = self.predictor.predict(color.permute(0, 2, 3, 1).contiguous()).depth.contiguous()
+                if self.on_hip:
+                    vmap.add(depth, color, all_poses[at:at + color.shape[0]])
+                if debug is not None or not self.on_hip:
+                    depths.append(depth)
+            if self.on_hip:
+                cloud = vmap.cloud(self.voxel, self.min_count)
+            else:
+                cloud = fuse_numpy(torch.cat(depths).numpy(), host_frames[first:last].numpy(), all_poses[first:last], inv_K, self.voxel,
+                                   min_count=self.min_count, **self.params)
+        if debug is not None:
+            debug["depth"], debug["poses"] = torch.cat(depths), all_poses
+        return cloud

@@ -122,6 +122,12 @@ SIGNATURES = {
     "td_lanczos_resize_u8": (_I, [_P, _P, _IARR, _P, ctypes.c_longlong, _IARR, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "td_lanczos_resize_u8_indexed": (_I, [_P, ctypes.c_longlong, _P, _LLARR, _P, _IARR, _P, ctypes.c_longlong, _IARR, _I, _I, _I, _I, _P,
                                           _P, _P]),
+    "td_cloud_keys": (_I, [_P, _P, _P, ctypes.POINTER(ctypes.c_double), _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                           _I, _I, ctypes.c_double, ctypes.c_double, _F, _P, _P, _P, _P]),
+    "td_cloud_heads": (_I, [_P, ctypes.c_longlong, _P, _P]),
+    "td_cloud_reduce_packed": (_I, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
+    "td_cloud_reduce_rows": (_I, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
+    "td_cloud_finish": (_I, [_P, _P, ctypes.c_longlong, ctypes.c_double, ctypes.c_longlong, _P, _P, _P, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}

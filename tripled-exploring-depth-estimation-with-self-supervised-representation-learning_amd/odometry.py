@@ -366,10 +366,11 @@ class OdometryEvaluator:
             axisangle, translation = net.PoseDecoder(net.PoseEncoder(pairs))
         return axisangle[:, 0].float(), translation[:, 0].float()
 
-    def relative_poses(self, dataset):
+    def relative_poses(self, dataset, frames=None):
         """float32 [n,4,4] on the evaluator's device: transformation_from_parameters(axisangle[:, 0], translation[:, 0]) of every
-        consecutive pair (frame i+1 -> frame i)."""
-        frames = dataset_frames_u8(dataset)
+        consecutive pair (frame i+1 -> frame i).  ``frames``: the dataset's frames as dataset_frames_u8 gives them, for a caller that
+        holds them already (on either device: they are not decoded or uploaded again)."""
+        frames = dataset_frames_u8(dataset) if frames is None else frames
         n = frames.shape[0] - 1
         net, restore = self._network()
         with torch.no_grad(), restore:
