@@ -113,3 +113,41 @@ def test_kernel_wrappers_refuse_host_tensors():
         evaluate.evaluate_disparity_hip(disp, gt, sizes, crops)
     with pytest.raises(native.NativeLibraryError):
         evaluate.masked_median_hip(torch.rand(2, 7))
+
+
+def test_require_device():
+    native.require_device()
+    with pytest.raises(native.NativeLibraryError, match=r"libtripled_hip needs device tensors \(got a cpu tensor\)"):
+        native.require_device(torch.zeros(1))
+    with pytest.raises(native.NativeLibraryError, match=r"libtripled_hip needs device tensors \(got a cpu tensor\)"):
+        native.ptr(torch.zeros(1))
+
+
+@pytest.mark.parametrize("wire", ["float32", "uint8"])
+def test_collate_validation_on_the_host(wire):
+    from mono.datasets import SyntheticTripletDataset, collate_validation
+    ds = SyntheticTripletDataset(2, 16, 24, with_gt=True, wire=wire)
+    samples = [ds[0], ds[1]]
+    batch = collate_validation(samples, "cpu")
+    assert "gt_depth" in samples[0] and "gt_depth" not in batch and "aug" not in batch
+    expanded = set()
+    if wire == "uint8":
+        assert "aug" in samples[0]
+        for f in ds.frame_ids:
+            u8 = torch.stack([s[("color_u8", f)] for s in samples], 0)
+            assert u8.dtype == torch.uint8 and ("color_u8", f) not in batch
+            assert batch[("color", f, 0)] is batch[("color_aug", f, 0)] and torch.equal(batch[("color", f, 0)], u8.float() / 255)
+            expanded |= {("color", f, 0), ("color_aug", f, 0)}
+    others = [k for k in samples[0] if k not in ("gt_depth", "aug") and not (isinstance(k, tuple) and k[0] == "color_u8")]
+    assert set(batch) == set(others) | expanded and len(others) >= 3
+    for k in others:
+        assert batch[k].dtype == torch.float32 and batch[k].shape[0] == 2
+        assert torch.equal(batch[k], torch.stack([torch.as_tensor(s[k]) for s in samples], 0).float())
+
+
+def test_collate_validation_refuses_raw_frames_on_the_host():
+    from mono.datasets import SyntheticTripletDataset, collate_validation
+    ds = SyntheticTripletDataset(1, 16, 24, frame_ids=(0,), with_gt=True, wire="raw_u8", raw_sizes=[(20, 30)])
+    assert ("raw_u8", 0) in ds[0]
+    with pytest.raises(native.NativeLibraryError, match="raw_u8"):
+        collate_validation([ds[0]], "cpu")

@@ -204,7 +204,7 @@ def test_evaluator_bf16_runs_the_folded_copy():
     model = _model()
     data = U.ListDataset(7, 5, 64, 128, U.MIXED_SIZES)
     ev = evaluate.DepthEvaluator(model, _dev(), batch_size=2, precision="bf16")
-    net, _ = ev._network()
+    net, _ = infer.eval_network(model, _dev(), "bf16")
     assert net is not model and infer.count_batchnorms(net.DepthEncoder) == 0
     mean, scales = ev.evaluate(data)
     assert scales.shape == (5,) and np.isfinite(scales).all() and all(np.isfinite(mean[k]) for k in evaluate.METRICS)

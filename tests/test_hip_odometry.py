@@ -42,11 +42,12 @@ def _d(a):
 
 # ---- 1. pairs ----------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n,h,w", [(2, 5, 7), (4, 8, 16), (3, 192, 640)])
+@pytest.mark.parametrize("n,h,w", [(2, 5, 7), (2, 8, 32), (4, 8, 16), (3, 192, 640)])
 def test_pairs_are_totensor_and_cat(n, h, w):
     g = torch.Generator().manual_seed(n * h)
     frames = torch.randint(0, 256, (n + 1, 3, h, w), generator=g, dtype=torch.uint8)
     frames[0, 0, 0, :5] = torch.tensor([0, 1, 127, 128, 255], dtype=torch.uint8)
+    frames.view(-1)[-256:] = torch.arange(256, dtype=torch.int64).to(torch.uint8)      # every byte value, in the scalar path too
     want = odometry.pairs_torch(frames)
     got = odometry.pairs_hip(frames.to(_dev()))
     assert got.dtype == torch.float32 and torch.equal(got.cpu(), want)

@@ -299,16 +299,16 @@ def test_expansion_refuses_another_store_and_float_offsets():
 
 
 def test_validation_collate_keeps_the_offsets():
-    """tripled_amd.evaluate._collate (DepthEvaluator's batches) on validation samples of both wires."""
+    """mono.datasets.collate_validation (DepthEvaluator's batches) on validation samples of both wires."""
     import tripled_amd  # noqa: F401
     from tripled_amd import resident
-    from tripled_amd.evaluate import _collate
+    from mono.datasets import collate_validation
     tree, stores = packed_tree()
     resident.get_store(stores[".jpg"], _dev(), RESERVE_GB)
     res_ds = dataset(tree, ".jpg", "resident", stores[".jpg"], frame_ids=[0], train=False)
     raw_ds = dataset(tree, ".jpg", "raw_u8", frame_ids=[0], train=False)
-    a = _collate([res_ds[i] for i in (0, 3)], _dev(), True)
-    b = _collate([raw_ds[i] for i in (0, 3)], _dev(), True)
+    a = collate_validation([res_ds[i] for i in (0, 3)], _dev())
+    b = collate_validation([raw_ds[i] for i in (0, 3)], _dev())
     assert set(a) == set(b) and torch.equal(a[("color", 0, 0)], b[("color", 0, 0)]) and a[("color", 0, 0)].shape == (2, 3, 16, 24)
 
 

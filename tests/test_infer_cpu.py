@@ -130,6 +130,43 @@ def test_predictor_keeps_the_callers_model():
         infer.DepthPredictor(model, 64, 96, "cpu", precision="bf16")
 
 
+# ---- the network the evaluators run ------------------------------------------------------------------------------------------
+
+def test_eval_network_fp32_runs_the_callers_model_and_restores_it():
+    model = build_model("cfg_kitti_fm", 32, 64).train()
+    net, restore = infer.eval_network(model, "cpu", "fp32")
+    assert net is model
+    with restore:
+        assert not any(m.training for m in model.modules())
+    assert model.training and all(m.training for m in model.modules())
+    net, restore = infer.eval_network(model, torch.device("cpu"), "fp32")
+    with pytest.raises(RuntimeError, match="inside"):
+        with restore:
+            assert not model.training
+            raise RuntimeError("inside")
+    assert net is model and all(m.training for m in model.modules())
+    net, restore = infer.eval_network(model.eval(), "cpu", "fp32")
+    with restore:
+        pass
+    assert not any(m.training for m in model.modules())          # the previous flag, not "training", comes back
+
+
+def test_eval_network_bf16_runs_a_folded_copy():
+    model = randomize_batchnorm(build_model("cfg_kitti_fm", 32, 64)).train()
+    before = {k: v.clone() for k, v in model.state_dict().items()}
+    n_bn = infer.count_batchnorms(model.DepthEncoder)
+    net, restore = infer.eval_network(model, "cpu", "bf16")
+    with restore:
+        assert net is not model and not any(m.training for m in net.modules())
+        assert n_bn > 0 and infer.count_batchnorms(net.DepthEncoder) == 0
+        assert sum(isinstance(m, torch.nn.Identity) for m in net.DepthEncoder.modules()) == n_bn
+        assert all(m.training for m in model.modules())
+    after = model.state_dict()
+    assert list(after) == list(before) and all(torch.equal(after[k], before[k]) and after[k].dtype == before[k].dtype for k in before)
+    assert all(m.training for m in model.modules()) and infer.count_batchnorms(model.DepthEncoder) == n_bn
+    assert next(model.parameters()).dtype == torch.float32
+
+
 # ---- script ------------------------------------------------------------------------------------------------------------------
 
 def test_infer_script_on_cpu(tmp_path):

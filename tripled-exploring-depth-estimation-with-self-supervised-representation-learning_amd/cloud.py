@@ -277,14 +277,8 @@ def load_ply(path):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the kernels
 
-def _device(*tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise native.NativeLibraryError("libtripled_hip needs device tensors (got a %s tensor)" % t.device)
-
-
 def _i64(t, name, n=None):
-    _device(t)
+    native.require_device(t)
     if t.dtype != torch.int64 or t.dim() != 1 or (n is not None and t.shape[0] != n):
         raise ValueError("%s: int64 [%s], got %s %s" % (name, "n" if n is None else n, tuple(t.shape), t.dtype))
     return t.contiguous()
@@ -295,7 +289,7 @@ def keys_hip(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_vo
     """keys_numpy as one launch of td_cloud_keys -> (key int64 [B H W], payload int64 [B H W]: the uint64's bits).  ``stats``: an int64
     [6] device tensor that the launch increments (the order of CAUSES), or None."""
     lib = native.load()
-    _device(depth, color, poses)
+    native.require_device(depth, color, poses)
     if depth.dtype != torch.float32 or depth.dim() != 3 or color.dtype != torch.uint8 or \
             tuple(color.shape) != (depth.shape[0], 3) + tuple(depth.shape[1:]) or poses.dtype != torch.float64 or \
             tuple(poses.shape) != (depth.shape[0], 3, 4):
@@ -338,7 +332,7 @@ def reduce_hip(sorted_keys, seg, perm, src, V):
     N, V = keys.shape[0], int(V)
     seg = _i64(seg, "seg", N)
     perm = None if perm is None else _i64(perm, "perm", N)
-    _device(src)
+    native.require_device(src)
     packed = src.dim() == 1
     if src.dtype != torch.int64 or not (packed or (src.dim() == 2 and src.shape[1] == 7)):
         raise ValueError("src: int64 [n] payloads or int64 [n,7] rows, got %s %s" % (tuple(src.shape), src.dtype))
@@ -359,7 +353,7 @@ def finish_hip(keys, sums, voxel, min_count=1):
     lib = native.load()
     keys = _i64(keys, "keys")
     V = keys.shape[0]
-    _device(sums)
+    native.require_device(sums)
     if sums.dtype != torch.int64 or tuple(sums.shape) != (V, 7):
         raise ValueError("sums: int64 [%d,7], got %s %s" % (V, tuple(sums.shape), sums.dtype))
     if not (np.isfinite(voxel) and voxel > 0):
@@ -389,7 +383,7 @@ def table_hip(key, src):
 def merge_hip(keys_a, sums_a, keys_b, sums_b):
     """Two voxel lists (unique keys, [.,7] rows) -> their union, rows of equal keys added: concatenate, table_hip."""
     keys_a, keys_b = _i64(keys_a, "keys_a"), _i64(keys_b, "keys_b")
-    _device(sums_a, sums_b)
+    native.require_device(sums_a, sums_b)
     for k, s in ((keys_a, sums_a), (keys_b, sums_b)):
         if s.dtype != torch.int64 or tuple(s.shape) != (k.shape[0], 7):
             raise ValueError("sums: int64 [%d,7], got %s %s" % (k.shape[0], tuple(s.shape), s.dtype))
@@ -424,7 +418,7 @@ def fuse_hip(depth, color, poses, inv_K, voxel=DEFAULT_VOXEL, batch_size=None, s
              max_range=DEFAULT_MAX_RANGE, edge=0.0, min_count=1, depth_scale=1.0, pose_scale=1.0):
     """fuse_numpy on the device, ``batch_size`` frames at a time (default: all at once) -> Cloud of device tensors."""
     _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
-    _device(depth, color, poses)
+    native.require_device(depth, color, poses)
     n = depth.shape[0]
     step = n if batch_size is None else int(batch_size)
     if step < 1 and n:
@@ -468,9 +462,7 @@ class SceneFuser:
                  min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=DEFAULT_EDGE, min_count=1, depth_scale=1.0,
                  pose_scale=1.0, post_process=False):
         _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
-        if int(batch_size) < 1:
-            raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
-        self.device = torch.device(device)
+        self.device = infer.check_precision(device, precision, batch_size)
         self.on_hip = self.device.type == "cuda"
         self.model = model
         self.batch_size, self.precision = int(batch_size), precision

@@ -314,8 +314,6 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_finish_kernel(const long lon
   keep[i] = n >= min_count ? 1 : 0;
 }
 
-static inline long long blocks_for(long long n) { return (n + TD_THREADS - 1) / TD_THREADS; }
-
 }  // namespace td
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -336,12 +334,11 @@ extern "C" int td_cloud_keys(const float* depth, const uint8_t* color, const dou
   a.edge = edge; a.key = key; a.payload = payload; a.stats = reinterpret_cast<unsigned long long*>(stats);
   // the widest run the row length and the four base pointers allow
   int vec = 4;
-  while (vec > 1 && (W % vec != 0 || (uintptr_t)depth % (4 * vec) != 0 || (uintptr_t)color % vec != 0 ||
-                     (uintptr_t)key % (8 * vec) != 0 || (uintptr_t)payload % (8 * vec) != 0))
+  while (vec > 1 && !(W % vec == 0 && td::aligned_to(depth, 4 * vec) && td::aligned_to(color, vec) && td::aligned_to(key, 8 * vec) &&
+                      td::aligned_to(payload, 8 * vec)))
     vec >>= 1;
-  const long long blocks = td::blocks_for((long long)B * H * (W / vec));
-  if (blocks > 0x7fffffffLL) return TD_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)blocks), block(TD_THREADS);
+  const dim3 grid(td::blocks_1d((long long)B * H * (W / vec))), block(TD_THREADS);
+  if (!grid.x) return TD_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   if (vec == 4) hipLaunchKernelGGL((td::cloud_keys_kernel<4>), grid, block, 0, s, a);
   else if (vec == 2) hipLaunchKernelGGL((td::cloud_keys_kernel<2>), grid, block, 0, s, a);
@@ -352,9 +349,9 @@ extern "C" int td_cloud_keys(const float* depth, const uint8_t* color, const dou
 extern "C" int td_cloud_heads(const long long* keys, long long N, int* flags, td_stream_t stream) {
   if (!keys || !flags || N < 0) return TD_ERR_BAD_ARG;
   if (N == 0) return TD_OK;
-  const long long blocks = td::blocks_for(N);
-  if (blocks > 0x7fffffffLL) return TD_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(td::cloud_heads_kernel, dim3((unsigned)blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, keys, N, flags);
+  const unsigned blocks = td::blocks_1d(N);
+  if (!blocks) return TD_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(td::cloud_heads_kernel, dim3(blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, keys, N, flags);
   return td::record_launch_error(hipGetLastError(), "td_cloud_heads");
 }
 
@@ -364,9 +361,9 @@ static int cloud_reduce(const long long* keys, const long long* seg, const long 
   if (!keys || !seg || !src || !out_keys || !sums || N < 0 || V < 0 || n_src < 0 || V > N) return TD_ERR_BAD_ARG;
   if (N == 0 || V == 0) return TD_OK;
   const long long waves = (N + TD_CLOUD_STRETCH - 1) / TD_CLOUD_STRETCH;
-  const long long blocks = (waves + TD_THREADS / 64 - 1) / (TD_THREADS / 64);
-  if (blocks > 0x7fffffffLL) return TD_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL((td::cloud_reduce_kernel<PACKED>), dim3((unsigned)blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, keys, seg,
+  const unsigned blocks = td::blocks_1d(waves * 64);
+  if (!blocks) return TD_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL((td::cloud_reduce_kernel<PACKED>), dim3(blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, keys, seg,
                      perm, src, n_src, N, V, out_keys, sums);
   return td::record_launch_error(hipGetLastError(), what);
 }
@@ -387,9 +384,9 @@ extern "C" int td_cloud_finish(const long long* keys, const long long* sums, lon
                                uint8_t* rgb, int* count, uint8_t* keep, td_stream_t stream) {
   if (!keys || !sums || !xyz || !rgb || !count || !keep || V < 0 || !(voxel > 0.0)) return TD_ERR_BAD_ARG;
   if (V == 0) return TD_OK;
-  const long long blocks = td::blocks_for(V);
-  if (blocks > 0x7fffffffLL) return TD_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(td::cloud_finish_kernel, dim3((unsigned)blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, keys, sums, V, voxel,
+  const unsigned blocks = td::blocks_1d(V);
+  if (!blocks) return TD_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(td::cloud_finish_kernel, dim3(blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, keys, sums, V, voxel,
                      min_count, xyz, rgb, count, keep);
   return td::record_launch_error(hipGetLastError(), "td_cloud_finish");
 }

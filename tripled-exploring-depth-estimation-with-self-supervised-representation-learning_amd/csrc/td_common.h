@@ -291,4 +291,14 @@ static inline int pick_rows(int units, int H, int halo, int step, int lo, int hi
   return best;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side of the one-thread-per-run launches (inference, evaluation, odometry, point cloud).
+static inline bool aligned_to(const void* p, size_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
+
+// Blocks of TD_THREADS that hold `threads` (>= 1) threads, or 0 when they do not fit a 1-D grid.
+static inline unsigned blocks_1d(long long threads) {
+  const long long b = (threads + TD_THREADS - 1) / TD_THREADS;
+  return b > 0x7fffffffLL ? 0u : (unsigned)b;
+}
+
 }  // namespace td

@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "td_common.h"
+#include "td_vec8.h"
 
 namespace td {
 namespace ev {
@@ -38,8 +39,11 @@ struct RowState {
 };
 static_assert(sizeof(RowState) == 64, "RowState layout");
 
-__device__ __forceinline__ float as_float(float v) { return v; }
-__device__ __forceinline__ float as_float(unsigned short v) { return __uint_as_float((unsigned)v << 16); }      // bf16 bits
+template <typename T>      // float, or bf16 bits as unsigned short
+__device__ __forceinline__ float as_float(T v) {
+  if constexpr (sizeof(T) == 2) return bf2f(v);
+  else return v;
+}
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
@@ -357,8 +361,6 @@ static void launch_select(const float* key, const float* v1, int B, long long n,
   }
 }
 
-static inline bool aligned_to(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
-
 }  // namespace ev
 }  // namespace td
 
@@ -379,7 +381,7 @@ extern "C" int td_eval_depth(const void* disp, int dtype, int B, int h, int w, f
   if (!disp || !gt || !sizes || !crops || !workspace || !metrics || !counts) return TD_ERR_BAD_ARG;
   if (B <= 0 || h <= 0 || w <= 0 || Hmax <= 0 || Wmax <= 0) return TD_ERR_BAD_ARG;
   if (!(min_depth >= 0.f) || !(max_depth > min_depth) || (stereo != 0 && stereo != 1)) return TD_ERR_BAD_ARG;
-  if (!aligned_to(workspace, 8)) return TD_ERR_BAD_ARG;
+  if (!td::aligned_to(workspace, 8)) return TD_ERR_BAD_ARG;
   if (dtype != TD_DTYPE_F32 && dtype != TD_DTYPE_BF16) return TD_ERR_UNSUPPORTED;
   const long long P = (long long)Hmax * Wmax;
   if (B > 65535 || P > (1LL << 30) || (long long)h * w > (1LL << 30)) return TD_ERR_UNSUPPORTED;
@@ -417,7 +419,7 @@ extern "C" int td_masked_median(const float* values, int B, long long n, void* w
                                 int* count, td_stream_t stream) {
   using namespace td::ev;
   if (!values || !workspace || !median || !count || B <= 0 || n <= 0) return TD_ERR_BAD_ARG;
-  if (!aligned_to(workspace, 4)) return TD_ERR_BAD_ARG;
+  if (!td::aligned_to(workspace, 4)) return TD_ERR_BAD_ARG;
   if (B > 65535 || n > 0x7fffffffLL) return TD_ERR_UNSUPPORTED;
   if (workspace_bytes < (long long)median_bytes(B)) return TD_ERR_WORKSPACE;
   char* ws = static_cast<char*>(workspace);

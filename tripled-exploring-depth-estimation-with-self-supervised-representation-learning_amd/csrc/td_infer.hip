@@ -11,6 +11,7 @@
 // threads, so each input byte comes from HBM once.  Coordinates follow ATen's upsample_bilinear2d (align_corners=False):
 // td::up_index.  The file is compiled with -ffp-contract=off: every product and sum below is rounded on its own.
 #include "td_common.h"
+#include "td_vec8.h"
 
 namespace td {
 
@@ -25,8 +26,11 @@ __device__ __forceinline__ void store_run(float* p, const float* v) {
   }
 }
 
-__device__ __forceinline__ float as_float(float v) { return v; }
-__device__ __forceinline__ float as_float(unsigned short v) { return __uint_as_float((unsigned)v << 16); }      // bf16 bits
+template <typename T>      // float, or bf16 bits as unsigned short
+__device__ __forceinline__ float as_float(T v) {
+  if constexpr (sizeof(T) == 2) return bf2f(v);
+  else return v;
+}
 
 // ---- image -> network input ----------------------------------------------------------------------------------------------
 // img [B,H0,W0,3] uint8 -> out [B*(1+mirror),3,h,w]; thread = V columns x 3 channels of one output row.
@@ -153,9 +157,6 @@ __global__ __launch_bounds__(TD_THREADS) void colorize_kernel(const float* __res
   }
 }
 
-static inline bool aligned_to(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) % bytes) == 0; }
-static inline bool fits_grid(long long threads) { return (threads + TD_THREADS - 1) / TD_THREADS <= 0x7fffffffLL; }
-
 }  // namespace td
 
 extern "C" int td_infer_preprocess(const uint8_t* img_u8, int B, int H0, int W0, int h, int w, int mirror, float* out,
@@ -165,9 +166,8 @@ extern "C" int td_infer_preprocess(const uint8_t* img_u8, int B, int H0, int W0,
   if ((long long)H0 * W0 * 3 > 0x7fffffffLL) return TD_ERR_UNSUPPORTED;      // tap offsets inside one image are ints
   const float ry = (float)H0 / (float)h, rx = (float)W0 / (float)w;
   const int V = (w % 4 == 0 && td::aligned_to(out, 16)) ? 4 : 1;
-  const long long threads = (long long)B * h * (w / V);
-  if (!td::fits_grid(threads)) return TD_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)((threads + TD_THREADS - 1) / TD_THREADS)), block(TD_THREADS);
+  const dim3 grid(td::blocks_1d((long long)B * h * (w / V))), block(TD_THREADS);
+  if (!grid.x) return TD_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (V == 4)
     hipLaunchKernelGGL((td::infer_preprocess_kernel<4>), grid, block, 0, st, img_u8, B, H0, W0, h, w, mirror, ry, rx, out);
@@ -180,8 +180,7 @@ template <typename T, bool PAIRED>
 static void launch_postprocess(const void* disp, int B, int h, int w, int H0, int W0, float a, float b, float depth_scale,
                                float* disp_out, float* depth_out, int V, hipStream_t st) {
   const float ry = (float)h / (float)H0, rx = (float)w / (float)W0;
-  const long long threads = (long long)B * H0 * (W0 / V);
-  const dim3 grid((unsigned)((threads + TD_THREADS - 1) / TD_THREADS)), block(TD_THREADS);
+  const dim3 grid(td::blocks_1d((long long)B * H0 * (W0 / V))), block(TD_THREADS);      // the caller has checked that it fits
   const T* d = (const T*)disp;
   if (V == 4)
     hipLaunchKernelGGL((td::disp_postprocess_kernel<T, PAIRED, 4>), grid, block, 0, st, d, B, h, w, H0, W0, ry, rx, a, b,
@@ -206,7 +205,7 @@ extern "C" int td_disp_postprocess(const void* disp, int dtype, int B, int h, in
       V = cand;
       break;
     }
-  if (!td::fits_grid((long long)B * H0 * (W0 / V))) return TD_ERR_UNSUPPORTED;
+  if (!td::blocks_1d((long long)B * H0 * (W0 / V))) return TD_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == TD_DTYPE_F32) {
     if (paired) launch_postprocess<float, true>(disp, B, h, w, H0, W0, a, b, depth_scale, disp_out, depth_out, V, st);
@@ -222,9 +221,8 @@ extern "C" int td_colorize(const float* x, int B, long long n, const float* vmin
                            uint8_t* out, td_stream_t stream) {
   if (!x || !vmin || !vmax || !lut || !out || B <= 0 || n <= 0) return TD_ERR_BAD_ARG;
   const int V = (n % 4 == 0 && td::aligned_to(x, 16) && td::aligned_to(out, 4)) ? 4 : 1;
-  const long long threads = (long long)B * (n / V);
-  if (!td::fits_grid(threads)) return TD_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)((threads + TD_THREADS - 1) / TD_THREADS)), block(TD_THREADS);
+  const dim3 grid(td::blocks_1d((long long)B * (n / V))), block(TD_THREADS);
+  if (!grid.x) return TD_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   if (V == 4) hipLaunchKernelGGL((td::colorize_kernel<4>), grid, block, 0, st, x, B, n, vmin, vmax, lut, out);
   else hipLaunchKernelGGL((td::colorize_kernel<1>), grid, block, 0, st, x, B, n, vmin, vmax, lut, out);

@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "td_common.h"
+#include "td_vec8.h"
 
 namespace td {
 
@@ -18,12 +19,6 @@ namespace td {
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // pairs
-
-__device__ __forceinline__ unsigned short bf16_bits(float f) {      // round to nearest even (finite input)
-  unsigned u = __float_as_uint(f);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
 
 // Pair i = cat(frame i, frame i+1) is the 6 H W contiguous bytes that start at frame i: a streaming conversion.
 // VEC = 8: one 8-byte load per thread (the caller guarantees 3 H W % 8 == 0 and aligned bases); VEC = 1: scalar.
@@ -46,10 +41,10 @@ __global__ __launch_bounds__(TD_THREADS) void pose_pairs_kernel(const uint8_t* _
     }
     if (BF16) {
       uint4 p;
-      p.x = bf16_bits(v[0]) | ((unsigned)bf16_bits(v[1]) << 16);
-      p.y = bf16_bits(v[2]) | ((unsigned)bf16_bits(v[3]) << 16);
-      p.z = bf16_bits(v[4]) | ((unsigned)bf16_bits(v[5]) << 16);
-      p.w = bf16_bits(v[6]) | ((unsigned)bf16_bits(v[7]) << 16);
+      p.x = f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
+      p.y = f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
+      p.z = f2bf(v[4]) | ((unsigned)f2bf(v[5]) << 16);
+      p.w = f2bf(v[6]) | ((unsigned)f2bf(v[7]) << 16);
       *reinterpret_cast<uint4*>(static_cast<unsigned short*>(out) + o) = p;
     } else {
       float4* dst = reinterpret_cast<float4*>(static_cast<float*>(out) + o);
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(TD_THREADS) void pose_pairs_kernel(const uint8_t* _
     }
   } else {
     const float v = (float)src[0] / 255.f;
-    if (BF16) static_cast<unsigned short*>(out)[o] = bf16_bits(v);
+    if (BF16) static_cast<unsigned short*>(out)[o] = f2bf(v);
     else static_cast<float*>(out)[o] = v;
   }
 }
@@ -375,11 +370,9 @@ extern "C" int td_pose_pairs_u8(const uint8_t* frames, int n, int H, int W, int 
       (dtype != TD_DTYPE_F32 && dtype != TD_DTYPE_BF16))
     return TD_ERR_BAD_ARG;
   const long long frame_elems = 3LL * H * W;
-  const bool vec = frame_elems % 8 == 0 && ((uintptr_t)frames % 8) == 0 && ((uintptr_t)out % 16) == 0;
-  const long long per_row = vec ? 2 * frame_elems / 8 : 2 * frame_elems;
-  const long long bx = (per_row + TD_THREADS - 1) / TD_THREADS;
-  if (bx > 0x7fffffffLL || count > 65535) return TD_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)bx, (unsigned)count), block(TD_THREADS);
+  const bool vec = frame_elems % 8 == 0 && td::aligned_to(frames, 8) && td::aligned_to(out, 16);
+  const dim3 grid(td::blocks_1d(vec ? 2 * frame_elems / 8 : 2 * frame_elems), (unsigned)count), block(TD_THREADS);
+  if (!grid.x || count > 65535) return TD_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   if (vec && dtype == TD_DTYPE_F32)
     hipLaunchKernelGGL((td::pose_pairs_kernel<8, false>), grid, block, 0, s, frames, frame_elems, first, out_first, out);

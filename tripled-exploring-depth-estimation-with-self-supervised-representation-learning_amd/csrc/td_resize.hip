@@ -281,10 +281,10 @@ extern "C" int td_lanczos_resize_u8(const uint8_t* src, const int* meta, const i
   int h_max = Hc, w_max = Wc;
   const int rc = td::plan_resize(desc, n_sizes, table_ints, H, W, Hc, Wc, &h_max, &w_max, &plan);
   if (rc == TD_ERR_BAD_ARG) return rc;
-  if (((uintptr_t)src & 3u) || N > 65535) return TD_ERR_UNSUPPORTED;
+  if (!td::aligned_to(src, 4) || N > 65535) return TD_ERR_UNSUPPORTED;
   if (rc != TD_OK) return rc;
   const long long total = (long long)N * 3 * Hc * Wc;
-  const int packed = ((W & 3) == 0 && ((uintptr_t)dst & 3u) == 0) ? 1 : 0;
+  const int packed = ((W & 3) == 0 && td::aligned_to(dst, 4)) ? 1 : 0;
   hipLaunchKernelGGL(td::lanczos_resize_kernel, dim3(plan.bands, 3, N), dim3(td::RS_THREADS), plan.lds, (hipStream_t)stream, src, meta,
                      tables, plan.bank, n_sizes, Hc, Wc, H, W, plan.band, plan.span_max, plan.Wp, plan.SW, total, packed, dst, status);
   return td::record_launch_error(hipGetLastError(), "td_lanczos_resize_u8");
@@ -314,9 +314,9 @@ extern "C" int td_lanczos_resize_u8_indexed(const uint8_t* store, long long stor
       if (offsets_host[n] < 0 || frame > store_bytes || offsets_host[n] > store_bytes - frame) return TD_ERR_BAD_ARG;
     }
   }
-  if (((uintptr_t)store & 3u) || N > 65535) return TD_ERR_UNSUPPORTED;
+  if (!td::aligned_to(store, 4) || N > 65535) return TD_ERR_UNSUPPORTED;
   if (rc != TD_OK) return rc;
-  const int packed = ((W & 3) == 0 && ((uintptr_t)dst & 3u) == 0) ? 1 : 0;
+  const int packed = ((W & 3) == 0 && td::aligned_to(dst, 4)) ? 1 : 0;
   hipLaunchKernelGGL(td::lanczos_resize_indexed_kernel, dim3(plan.bands, 3, N), dim3(td::RS_THREADS), plan.lds, (hipStream_t)stream, store,
                      store_bytes, offsets, meta, tables, plan.bank, n_sizes, H, W, plan.band, plan.span_max, plan.Wp, plan.SW, packed, dst,
                      status);

@@ -15,8 +15,6 @@ Three layers, as in infer.py:
 Deviation from the host path: the interpolation is float32 where eval_hooks.resize_bilinear interpolates in float64 and rounds
 once (DESIGN.md section 15 has the measured distance); the coordinate is float64 in both.
 """
-import contextlib
-
 import numpy as np
 import torch
 
@@ -141,9 +139,7 @@ def evaluate_disparity_hip(disp, gt, sizes, crops, stereo_scale=False, affine=No
     crops: pad_ground_truth's, on the same HIP device.  No synchronisation: the results are device tensors."""
     lib = native.load()
     disp = _as_planes(disp)
-    for t in (disp, gt, sizes, crops):
-        if not t.is_cuda:
-            raise native.NativeLibraryError("libtripled_hip needs device tensors (got a %s tensor)" % t.device)
+    native.require_device(disp, gt, sizes, crops)
     if disp.dtype not in native.DTYPE_CODES:
         raise ValueError("disp: fp32 / bf16, got %s" % disp.dtype)
     B, h, w = disp.shape
@@ -170,10 +166,9 @@ def masked_median_hip(values):
     """float32 [B,n] on a HIP device, an entry <= 0 is absent -> (np.median of each row's present entries float32 [B] (NaN where
     there are none), their number int32 [B])."""
     lib = native.load()
-    native.ptr(values)
+    native.ptr(values)          # device and contiguous
     if values.dim() != 2 or values.dtype != torch.float32 or values.numel() == 0:
         raise ValueError("values: non-empty float32 [B,n], got %s %s" % (tuple(values.shape), values.dtype))
-    values = values.contiguous()
     B, n = values.shape
     need = lib.td_masked_median_workspace_bytes(B)
     workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=values.device)
@@ -185,33 +180,6 @@ def masked_median_hip(values):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-
-def _collate(samples, device, on_hip):
-    """Validation samples (dicts without 'gt_depth') -> one network batch on the device.  ("color_u8", f) frames are expanded by
-    the HIP kernel on the device (expand_device_batch) and by plain ToTensor on the host, as the evaluation hooks do."""
-    batch = {}
-    for k in samples[0]:
-        stacked = torch.stack([torch.as_tensor(s[k]) for s in samples], 0)
-        if k in ("raw_spec", "res_bytes"):               # raw_wire.HOST_KEYS: read by the host in the expansion
-            batch[k] = stacked
-            continue
-        if k == "raw_meta" or (isinstance(k, tuple) and k and k[0] in ("raw_u8", "res_off")):
-            batch[k] = stacked.to(device)                # bytes / int32; resized by the HIP kernel (a host batch raises there)
-            continue
-        if isinstance(k, tuple) and k and k[0] == "color_u8":
-            if on_hip:
-                batch[k] = stacked.to(device)
-            else:
-                img = stacked.float().div(255.0)
-                batch[("color", k[1], 0)], batch[("color_aug", k[1], 0)] = img, img
-            continue
-        batch[k] = stacked.float().to(device)
-    if on_hip or "raw_meta" in batch:
-        from mono.datasets import expand_device_batch
-        expand_device_batch(batch)
-    batch.pop("aug", None)
-    return batch
-
 
 def _with_mirrored(batch):
     """Entries B..2B-1 = the horizontally mirrored frames (images: 4-D tensors); everything else is repeated."""
@@ -231,14 +199,8 @@ class DepthEvaluator:
     """
 
     def __init__(self, model, device, batch_size=12, precision="fp32", post_process=False, stereo_scale=False):
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision: 'fp32' or 'bf16', got %r" % (precision,))
-        if int(batch_size) < 1:
-            raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
-        self.device = torch.device(device)
+        self.device = infer.check_precision(device, precision, batch_size)
         self.on_hip = self.device.type == "cuda"
-        if precision == "bf16" and not self.on_hip:
-            raise ValueError("precision='bf16' is the HIP device's path; the host path is fp32")
         self.model = model
         self.batch_size = int(batch_size)
         self.precision = precision
@@ -246,22 +208,11 @@ class DepthEvaluator:
         self.stereo_scale = bool(stereo_scale)
         self._workspace = None
 
-    def _network(self):
-        """(module to run, context that restores what was changed)."""
-        if self.precision == "bf16":
-            return infer.fold_batchnorm(self.model).to(self.device).eval(), contextlib.nullcontext()
-        p = next(self.model.parameters(), None)
-        here = p is None or (p.device.type == self.device.type and (self.device.index is None or p.device.index == self.device.index))
-        if not here:
-            return infer._own_copy(self.model).to(self.device).eval(), contextlib.nullcontext()
-        return self.model, _eval_mode(self.model)
-
     def _forward(self, net, batch):
         if self.precision == "bf16":
             batch = {k: v.contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v for k, v in batch.items()}
-            with torch.autocast("cuda", dtype=torch.bfloat16):
-                return net(batch)[("disp", 0, 0)]
-        return net(batch)[("disp", 0, 0)]
+        with infer.autocast_for(self.precision):
+            return net(batch)[("disp", 0, 0)]
 
     def score(self, disp_net, gt_list):
         """Network disparity [B*(1+post_process),1,h,w] + B ground truths -> ([B,8], [B]) on the device."""
@@ -284,13 +235,14 @@ class DepthEvaluator:
         indices = list(range(len(dataset))) if indices is None else list(indices)
         if not indices:
             return np.zeros((0, 8), np.float32), np.zeros((0,), np.int32)
-        net, restore = self._network()
+        from mono.datasets import collate_validation
+        net, restore = infer.eval_network(self.model, self.device, self.precision)
         rows, counts = [], []
         with torch.no_grad(), restore:
             for at in range(0, len(indices), self.batch_size):
                 samples = [dataset[i] for i in indices[at:at + self.batch_size]]
                 gts = [np.asarray(s["gt_depth"], dtype=np.float32) for s in samples]
-                batch = _collate([{k: v for k, v in s.items() if k != "gt_depth"} for s in samples], self.device, self.on_hip)
+                batch = collate_validation(samples, self.device)
                 if self.post_process:
                     batch = _with_mirrored(batch)
                 m, c = self.score(self._forward(net, batch), gts)
@@ -308,13 +260,3 @@ class DepthEvaluator:
         rows, _ = self.evaluate_rows(dataset)
         mean = {k: float(np.mean(rows[:, j].astype(np.float64))) for j, k in enumerate(METRICS)}
         return mean, rows[:, 7].astype(np.float64)
-
-
-@contextlib.contextmanager
-def _eval_mode(model):
-    was_training = model.training
-    model.eval()
-    try:
-        yield
-    finally:
-        model.train(was_training)

@@ -10,7 +10,7 @@ from mono.core import DistEvalMonoHook, DistOptimizerHook, NonDistEvalHook
 from mono.datasets import build_dataloader
 
 
-def _device():
+def _training_device():
     return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
 
 
@@ -58,7 +58,7 @@ def stage_inputs(data):
     """Every entry of the batch dict -> float32 on the training device (frames of the 'uint8' wire format stay bytes).
     The copies are issued non-blocking (asynchronous when the loader pins memory; no-ops behind DevicePrefetcher)."""
     from mono.datasets.raw_wire import HOST_KEYS, keeps_dtype
-    dev = _device()
+    dev = _training_device()
     for k, v in data.items():
         if k in HOST_KEYS:                                          # 'raw_u8' wire format: read by the host in the expansion
             continue
@@ -77,7 +77,7 @@ def change_input_variable(data):
         from mono.datasets import expand_device_batch
         expand_device_batch(data)
     else:
-        dev = _device()
+        dev = _training_device()
         data[0] = [torch.as_tensor(img).to(dev, dtype=torch.float32, non_blocking=True) for img in data[0]]
     return data
 
@@ -245,7 +245,7 @@ def _finish_runner(runner, cfg, data_loaders):
     if data_cfg.get("wire", "float32") == "resident":
         # the frames move into device memory now, before the first (eager) iteration: a store cannot be loaded during the capture
         from tripled_amd import resident
-        resident.get_store(data_cfg["store"], _device(), data_cfg.get("resident_reserve_gb", None))
+        resident.get_store(data_cfg["store"], _training_device(), data_cfg.get("resident_reserve_gb", None))
     data_loaders = _maybe_prefetch(data_loaders, cfg)
     if cfg.resume_from:
         runner.resume(cfg.resume_from)
@@ -256,7 +256,7 @@ def _finish_runner(runner, cfg, data_loaders):
 
 def _dist_train(model, dataset_train, dataset_val, cfg, validate=False):
     data_loaders = _loaders(dataset_train, cfg, dist=True)
-    dev = _device()
+    dev = _training_device()
     if cfg.get("syncbn", False):
         # this build's BatchNorm layers exchange their statistics themselves (hand-written passes + one small
         # all-reduce per layer and direction); any other normalisation layer takes torch's SyncBatchNorm
@@ -289,7 +289,7 @@ def _dist_train(model, dataset_train, dataset_val, cfg, validate=False):
 
 def _non_dist_train(model, dataset_train, dataset_val, cfg, validate=False):
     data_loaders = _loaders(dataset_train, cfg, dist=False)
-    dev = _device()
+    dev = _training_device()
     model = MMDataParallel(configure_execution(model, cfg, dev), device_ids=list(range(len(cfg.gpus))))
     use_graph = _use_hip_graph(cfg, dev, model)
     flat, processor = None, batch_processor

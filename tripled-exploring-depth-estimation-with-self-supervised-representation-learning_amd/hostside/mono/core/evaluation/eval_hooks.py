@@ -58,34 +58,18 @@ def evaluate_disparity(pred_disp, gt_depth, stereo_scale=False):
     return out
 
 
-def _predict_one(model, sample):
-    """dataset[idx] -> scaled disparity [h, w] (numpy) and ground-truth depth."""
-    dev = next(model.parameters()).device
-    batch = {}
-    for k, v in sample.items():
-        t = torch.as_tensor(v)
-        if k in ("raw_spec", "res_bytes"):               # raw_wire.HOST_KEYS: read by the host in the expansion
-            batch[k] = t.unsqueeze(0)
-            continue
-        if k == "raw_meta" or (isinstance(k, tuple) and k and k[0] in ("raw_u8", "res_off")):
-            batch[k] = t.unsqueeze(0).to(dev)            # bytes / int32; resized by the HIP kernel (no host path: a CPU model raises)
-            continue
-        if isinstance(k, tuple) and k and k[0] == "color_u8":
-            if dev.type == "cuda":                       # 'uint8' wire format: expanded by the HIP kernel below
-                batch[k] = t.unsqueeze(0).to(dev)
-            else:                                        # evaluation on the host: plain ToTensor (no jitter in validation)
-                img = t.float().div(255.0).unsqueeze(0)
-                batch[("color", k[1], 0)], batch[("color_aug", k[1], 0)] = img, img
-            continue
-        batch[k] = t.float().unsqueeze(0).to(dev)
-    if dev.type == "cuda" or "raw_meta" in batch:
-        from mono.datasets import expand_device_batch
-        expand_device_batch(batch)
-    batch.pop("aug", None)
+def _full_precision(model):
+    """The context validation runs under: the flat store's fp32 master weights if the model has one, as the reference does."""
     inner = model.module if hasattr(model, "module") else model
     flat = getattr(inner, "_flat_store", None)
-    ctx = flat.full_precision() if flat is not None else contextlib.nullcontext()
-    with torch.no_grad(), ctx:        # (flat store: validate on the fp32 master weights, as the reference does)
+    return flat.full_precision() if flat is not None else contextlib.nullcontext()
+
+
+def _predict_one(model, sample):
+    """dataset[idx] -> scaled disparity [h, w] (numpy) and ground-truth depth."""
+    from mono.datasets import collate_validation
+    batch = collate_validation([sample], next(model.parameters()).device)
+    with torch.no_grad(), _full_precision(model):
         result = model(batch)
     scaled, _ = disp_to_depth(result[("disp", 0, 0)].float())
     gt = torch.as_tensor(sample["gt_depth"]).float().cpu().numpy()
@@ -98,11 +82,8 @@ def _evaluate_on_device(model, dataset, indices, stereo, cfg):
     full-precision context as _predict_one.  Returns {index: per-image metric dict}, as the default loop builds."""
     from tripled_amd.evaluate import COLUMNS, DepthEvaluator
     dev = next(model.parameters()).device
-    inner = model.module if hasattr(model, "module") else model
-    flat = getattr(inner, "_flat_store", None)
-    ctx = flat.full_precision() if flat is not None else contextlib.nullcontext()
     indices = list(indices)
-    with ctx:
+    with _full_precision(model):
         rows, _ = DepthEvaluator(model, dev, batch_size=int(cfg.get("validate_batch_size", 12)),
                                  stereo_scale=stereo).evaluate_rows(dataset, indices)
     return {i: dict(zip(COLUMNS, (float(v) for v in row))) for i, row in zip(indices, rows)}

@@ -2,7 +2,7 @@ from .loader import DistributedGroupSampler, DistributedSampler, GroupSampler, b
 from .get_dataset import get_dataset  # noqa: F401
 from .synthetic import ResidentBatches, SyntheticTripletDataset, synthetic_batch  # noqa: F401
 from .prefetch import DevicePrefetcher  # noqa: F401
-from .device_expand import expand_device_batch, has_uint8_frames  # noqa: F401
+from .device_expand import collate_validation, expand_device_batch, has_uint8_frames  # noqa: F401
 
 
 def __getattr__(name):      # the KITTI classes need PIL: imported on first use

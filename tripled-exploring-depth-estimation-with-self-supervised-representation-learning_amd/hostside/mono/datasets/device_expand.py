@@ -96,3 +96,32 @@ def expand_device_batch(data):
         del data[k]
     del data["aug"]
     return data
+
+
+def collate_validation(samples, device):
+    """Validation samples (dataset[i] dicts) -> one network batch on ``device``: what DepthEvaluator and the evaluation hooks feed
+    the model.  ("color_u8", f) frames are expanded by the HIP kernel on the device (expand_device_batch) and by plain ToTensor on
+    the host (no jitter in validation).  "gt_depth" stays with the sample (no model reads it) and "aug" is dropped."""
+    device = torch.device(device)
+    on_hip = device.type == "cuda"
+    batch = {}
+    for k in samples[0]:
+        if k == "gt_depth":
+            continue
+        stacked = torch.stack([torch.as_tensor(s[k]) for s in samples], 0)
+        if k in ("raw_spec", "res_bytes"):               # raw_wire.HOST_KEYS: read by the host in the expansion
+            batch[k] = stacked
+        elif k == "raw_meta" or (isinstance(k, tuple) and k and k[0] in ("raw_u8", "res_off")):
+            batch[k] = stacked.to(device)                # bytes / int32; resized by the HIP kernel (a host batch raises there)
+        elif isinstance(k, tuple) and k and k[0] == "color_u8":
+            if on_hip:
+                batch[k] = stacked.to(device)
+            else:
+                img = stacked.float().div(255.0)
+                batch[("color", k[1], 0)], batch[("color_aug", k[1], 0)] = img, img
+        else:
+            batch[k] = stacked.float().to(device)
+    if on_hip or "raw_meta" in batch:
+        expand_device_batch(batch)
+    batch.pop("aug", None)
+    return batch

@@ -16,6 +16,7 @@ Three layers here:
 Nothing here imports matplotlib: the colour table is 256 rows of data (magma_lut.txt, next to this file).
 """
 import collections
+import contextlib
 import copy
 import os
 
@@ -129,7 +130,7 @@ def _device_lut(device):
 def preprocess_hip(images, height, width, mirror=False):
     """preprocess_torch as one launch of td_infer_preprocess; ``images``: uint8 [B,H0,W0,3] on a HIP device."""
     lib = native.load()
-    native.ptr(images)
+    native.ptr(images)          # device and contiguous: the input is never copied
     if images.dim() != 4 or images.shape[3] != 3 or images.dtype != torch.uint8:
         raise ValueError("images: uint8 [B,H0,W0,3], got %s %s" % (tuple(images.shape), images.dtype))
     B, H0, W0 = images.shape[:3]
@@ -148,8 +149,8 @@ def postprocess_hip(disp, out_h, out_w, paired=False, a=None, b=None, depth_scal
         raise ValueError("disp: fp32 / bf16 [N,1,h,w], got %s %s" % (tuple(disp.shape), disp.dtype))
     if paired and disp.shape[0] % 2:
         raise ValueError("paired post-processing needs an even batch, got %d" % disp.shape[0])
+    native.require_device(disp)
     disp = disp.contiguous()
-    native.ptr(disp)
     B = disp.shape[0] // (2 if paired else 1)
     h, w = disp.shape[2:]
     d = torch.empty(B, out_h, out_w, device=disp.device, dtype=torch.float32)
@@ -241,6 +242,49 @@ def count_batchnorms(module):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# which network runs, and how: shared by DepthPredictor, evaluate.DepthEvaluator, odometry.OdometryEvaluator and cloud.SceneFuser
+
+def check_precision(device, precision, batch_size=None):
+    """The constructors' argument check -> torch.device(device): 'fp32' runs on either device, 'bf16' on the HIP device only."""
+    if precision not in ("fp32", "bf16"):
+        raise ValueError("precision: 'fp32' or 'bf16', got %r" % (precision,))
+    if batch_size is not None and int(batch_size) < 1:
+        raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
+    device = torch.device(device)
+    if precision == "bf16" and device.type != "cuda":
+        raise ValueError("precision='bf16' is the HIP device's path; the host path is fp32")
+    return device
+
+
+def autocast_for(precision):
+    """The context a network call runs under: bf16 autocast for 'bf16' (whose callers hand the network channels-last inputs),
+    nothing for 'fp32'."""
+    return torch.autocast("cuda", dtype=torch.bfloat16) if precision == "bf16" else contextlib.nullcontext()
+
+
+@contextlib.contextmanager
+def eval_mode(model):
+    """``model`` in eval mode; its previous training flag comes back on exit, also when the body raises."""
+    was_training = model.training
+    model.eval()
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+def eval_network(model, device, precision):
+    """(network to run, context that restores what was changed).  bf16: the BatchNorm-folded copy on ``device``; fp32 with the
+    model on another device: its own copy there; fp32 with the model on ``device`` (a model without parameters counts as there,
+    and a device without an index matches any): the caller's model itself, inside eval_mode.  The caller's model is never moved."""
+    device = torch.device(device)
+    if precision == "bf16":
+        return fold_batchnorm(model).to(device).eval(), contextlib.nullcontext()
+    p = next(model.parameters(), None)
+    if p is None or (p.device.type == device.type and (device.index is None or p.device.index == device.index)):
+        return model, eval_mode(model)
+    return _own_copy(model).to(device).eval(), contextlib.nullcontext()
+
 
 def network_inputs(x):
     """The evaluation batch of a depth model: no augmentation at inference, so the frame is both ("color", 0, 0) and
@@ -263,12 +307,8 @@ class DepthPredictor:
 
     def __init__(self, model, height, width, device, precision="fp32", post_process=False, min_depth=0.1, max_depth=100.0,
                  depth_scale=1.0, affine=None):
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision: 'fp32' or 'bf16', got %r" % (precision,))
-        self.device = torch.device(device)
+        self.device = check_precision(device, precision)
         self.on_hip = self.device.type == "cuda"
-        if precision == "bf16" and not self.on_hip:
-            raise ValueError("precision='bf16' is the HIP device's path; the host path is fp32")
         self.height, self.width = int(height), int(width)
         self.precision = precision
         self.post_process = bool(post_process)
@@ -309,11 +349,9 @@ class DepthPredictor:
 
     def forward(self, x):
         """network input -> network-size disparity [N,1,height,width] (bf16 in the bf16 path)."""
-        with torch.no_grad():
-            if self.precision == "bf16":
-                x = x.contiguous(memory_format=torch.channels_last)
-                with torch.autocast("cuda", dtype=torch.bfloat16):
-                    return self.model(network_inputs(x))[("disp", 0, 0)]
+        if self.precision == "bf16":
+            x = x.contiguous(memory_format=torch.channels_last)
+        with torch.no_grad(), autocast_for(self.precision):
             return self.model(network_inputs(x))[("disp", 0, 0)]
 
     def postprocess(self, disp_net, out_h, out_w):

@@ -176,12 +176,18 @@ def check(code, what):
         raise NativeLibraryError("%s failed: %s (%d)%s" % (what, msg, code, (" [" + hip + "]") if hip else ""))
 
 
+def require_device(*tensors):
+    """The guard of every kernel wrapper: a tensor that is not on a HIP device is an error, never a silent host path."""
+    for t in tensors:
+        if not t.is_cuda:
+            raise NativeLibraryError("libtripled_hip needs device tensors (got a %s tensor)" % t.device)
+
+
 def ptr(t):
     """Device pointer of a tensor (None -> NULL).  The tensor must be a dense CUDA/HIP tensor."""
     if t is None:
         return None
-    if not t.is_cuda:
-        raise NativeLibraryError("libtripled_hip needs device tensors (got a %s tensor)" % t.device)
+    require_device(t)
     if not t.is_contiguous():
         raise NativeLibraryError("libtripled_hip needs contiguous tensors")
     return ctypes.c_void_p(t.data_ptr())

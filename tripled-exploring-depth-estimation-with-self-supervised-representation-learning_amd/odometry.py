@@ -20,7 +20,6 @@ Deviations from the reference (DESIGN.md section 16 has the measured distances):
 before it is inverted (np.linalg.inv of a float32 array stays in float32), and the in-memory poses are scored, not their %1.8e text.
 """
 import collections
-import contextlib
 import ctypes
 
 import numpy as np
@@ -196,21 +195,15 @@ def segment_errors(rows, lengths=LENGTHS):
 # ---------------------------------------------------------------------------------------------------------------------------
 # the kernels
 
-def _device(*tensors):
-    for t in tensors:
-        if not t.is_cuda:
-            raise native.NativeLibraryError("libtripled_hip needs device tensors (got a %s tensor)" % t.device)
-
-
 def _rel(rel):
-    _device(rel)
+    native.require_device(rel)
     if rel.dim() != 3 or tuple(rel.shape[1:]) != (4, 4) or rel.shape[0] < 1 or rel.dtype not in (torch.float32, torch.float64):
         raise ValueError("rel: float32 / float64 [n,4,4] with n >= 1, got %s %s" % (tuple(rel.shape), rel.dtype))
     return rel.contiguous(), 1 if rel.dtype == torch.float64 else 0
 
 
 def _poses(p, name, m=None):
-    _device(p)
+    native.require_device(p)
     if p.dim() != 3 or tuple(p.shape[1:]) != (3, 4) or p.dtype != torch.float64 or (m is not None and p.shape[0] != m):
         raise ValueError("%s: float64 [%s,3,4], got %s %s" % (name, "m" if m is None else m, tuple(p.shape), p.dtype))
     return p.contiguous()
@@ -229,7 +222,7 @@ def pairs_hip(frames, dtype=torch.float32, first=0, count=None, out=None, out_fi
     Without ``out`` a new [count,6,H,W]; with ``out`` [.,6,H,W] the pairs go to its rows out_first ... (default: ``first``, a window
     of the full [n,6,H,W] array; 0 fills a batch buffer) and the other rows are left alone."""
     lib = native.load()
-    _device(frames)
+    native.require_device(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] < 2:
         raise ValueError("frames: uint8 [n+1,3,H,W] with n >= 1, got %s %s" % (tuple(frames.shape), frames.dtype))
     if dtype not in native.DTYPE_CODES:
@@ -241,7 +234,7 @@ def pairs_hip(frames, dtype=torch.float32, first=0, count=None, out=None, out_fi
     if out is None:
         out, out_first = torch.empty(count, 6, H, W, dtype=dtype, device=frames.device), 0
     else:
-        _device(out)
+        native.require_device(out)
         out_first = first if out_first is None else int(out_first)
         if out.dim() != 4 or tuple(out.shape[1:]) != (6, H, W) or out.dtype != dtype or not out.is_contiguous() or \
                 out_first < 0 or out_first + count > out.shape[0]:
@@ -334,14 +327,8 @@ class OdometryEvaluator:
     """
 
     def __init__(self, model, device, batch_size=12, precision="fp32"):
-        if precision not in ("fp32", "bf16"):
-            raise ValueError("precision: 'fp32' or 'bf16', got %r" % (precision,))
-        if int(batch_size) < 1:
-            raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
-        self.device = torch.device(device)
+        self.device = infer.check_precision(device, precision, batch_size)
         self.on_hip = self.device.type == "cuda"
-        if precision == "bf16" and not self.on_hip:
-            raise ValueError("precision='bf16' is the HIP device's path; the host path is fp32")
         for part in ("PoseEncoder", "PoseDecoder"):
             if not hasattr(model, part):
                 raise TypeError("model: no %s" % part)
@@ -349,20 +336,10 @@ class OdometryEvaluator:
         self.batch_size = int(batch_size)
         self.precision = precision
 
-    def _network(self):
-        if self.precision == "bf16":
-            return infer.fold_batchnorm(self.model).to(self.device).eval(), contextlib.nullcontext()
-        p = next(self.model.parameters(), None)
-        here = p is None or (p.device.type == self.device.type and (self.device.index is None or p.device.index == self.device.index))
-        if not here:
-            return infer._own_copy(self.model).to(self.device).eval(), contextlib.nullcontext()
-        return self.model, _eval_mode(self.model)
-
     def _pose_vectors(self, net, pairs):
         if self.precision == "bf16":
-            with torch.autocast("cuda", dtype=torch.bfloat16):
-                axisangle, translation = net.PoseDecoder(net.PoseEncoder(pairs.contiguous(memory_format=torch.channels_last)))
-        else:
+            pairs = pairs.contiguous(memory_format=torch.channels_last)
+        with infer.autocast_for(self.precision):
             axisangle, translation = net.PoseDecoder(net.PoseEncoder(pairs))
         return axisangle[:, 0].float(), translation[:, 0].float()
 
@@ -372,7 +349,7 @@ class OdometryEvaluator:
         holds them already (on either device: they are not decoded or uploaded again)."""
         frames = dataset_frames_u8(dataset) if frames is None else frames
         n = frames.shape[0] - 1
-        net, restore = self._network()
+        net, restore = infer.eval_network(self.model, self.device, self.precision)
         with torch.no_grad(), restore:
             if not self.on_hip:
                 pairs = pairs_torch(frames)
@@ -430,13 +407,3 @@ class OdometryEvaluator:
         with np.errstate(invalid="ignore"):
             ate_mean, ate_std = float(np.mean(ates)), float(np.std(ates))
         return OdometryResult(ate_mean, ate_std, t_err, r_err, scale, distance, poses, ates, rows, rel)
-
-
-@contextlib.contextmanager
-def _eval_mode(model):
-    was_training = model.training
-    model.eval()
-    try:
-        yield
-    finally:
-        model.train(was_training)
