@@ -776,6 +776,40 @@ int td_cloud_reduce_rows(const long long* keys, const long long* seg, const long
 int td_cloud_finish(const long long* keys, const long long* sums, long long V, double voxel, long long min_count, float* xyz,
                     uint8_t* rgb, int* count, uint8_t* keep, td_stream_t stream);
 
+/*
+ * KITTI ground-truth depth maps from velodyne scans, a batch of frames of different sizes per call (csrc/td_velo.hip,
+ * tripled_amd/velodyne.py).  Replaces generate_depth_map, mono/datasets/kitti_utils.py:50-102 (the projection :71-86, the last-write
+ * scatter :89-90, the duplicate rule with sub2ind :43-47,93-99, the clamp :100), which KITTIRAWDataset.get_depth calls per frame,
+ * mono/datasets/kitti_dataset.py:201-215; the scipy.misc.imresize of :210 is not part of it (the evaluation reads native size).
+ *
+ * td_velo_depth: two fills and two launches whatever B is, no synchronisation, no copy to the host, no allocation.
+ *   points [Ntot,4] float32 (x forward, y left, z up, reflectance: column 3 is never read), the frames' scans concatenated, 4-byte
+ *        aligned (a 16-byte aligned base is read 16 bytes at a time);  offsets [B+1] int64 (device): frame b owns points
+ *        offsets[b] .. offsets[b+1]-1;  P [B,3,4] float64 (device) = P_rect_0c . R_rect_00 . [R|T]_velo_to_cam, multiplied on the host
+ *   sizes [B,2] int32 (device) = (H, W) per frame.  The host never reads it: a frame with H outside 1..Hmax, W outside 2..Wmax or
+ *        offsets that run backwards gets an all-zero map and a stats row of -1
+ *   per point, float64, every product and sum rounded on its own:
+ *        kept when x >= 0 (float32 compare; -0.0 passes);  r_k = ((P_k0 x + P_k1 y) + P_k2 z) + P_k3;
+ *        u = rint(r_0 / r_2) - 1, v = rint(r_1 / r_2) - 1 (half to even);  valid when 0 <= u < W and 0 <= v < H (NaN and inf fail,
+ *        r_2 < 0 can pass);  d = r_2, or (double)x with vel_depth
+ *   per pixel: d of the LAST valid point on it, in file order.  Points are grouped by g = v (W-1) + u - 1 (pixel (v, W-1) shares a
+ *        group with pixel (v+1, 0); g = -1 is pixel (0,0)): for a group of more than one point, the pixel of the group's FIRST point
+ *        is overwritten with the minimum d of the whole group.  Values < 0 become 0, pixels nobody hit are 0.
+ *   gt [B,Hmax,Wmax] float32 (out), written completely: frame b occupies the top-left sizes[b], the padding is 0 (the layout of
+ *        td_eval_depth's gt)
+ *   stats [B,6] int64 (out): points, behind (x < 0), outside (kept but not valid, a NaN x included), valid, pixels hit, pixels
+ *        clamped from negative to 0
+ *   workspace: td_velo_depth_workspace_bytes(B, Hmax, Wmax) bytes (0: unsupported shape), 8-byte aligned: four tables of 64-bit
+ *        integers, one entry per pixel and three per group (H (W-1) + 1 groups per frame)
+ *   TD_ERR_BAD_ARG before any launch: a null pointer, B <= 0, Hmax < 1, Wmax < 2, a workspace that is too small or misaligned.
+ *   Every table entry is a 64-bit integer minimum (a maximum of indices as the minimum of the complements of index + 1, a minimum of doubles
+ *   through an order-preserving map of their bits; -0.0 sorts below +0.0): no floating-point atomics, no kernel waits on another
+ *   workgroup, two calls on the same inputs return the same bits.
+ */
+long long td_velo_depth_workspace_bytes(int B, int Hmax, int Wmax);
+int td_velo_depth(const float* points, const long long* offsets, int B, const double* P, const int* sizes, int Hmax, int Wmax,
+                  int vel_depth, void* workspace, long long workspace_bytes, float* gt, long long* stats, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

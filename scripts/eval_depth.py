@@ -5,6 +5,10 @@ disparity of every validation frame, resize to the ground-truth size, median-sca
 
   python scripts/eval_depth.py --config config/cfg_kitti_tripleD.py --checkpoint work/epoch_20.pth \
          --gt_depths /data/kitti_raw/gt_depths.npz [--batch_size 12 [--precision bf16] [--post_process]]
+  python scripts/eval_depth.py --config config/cfg_kitti_tripleD.py --checkpoint work/epoch_20.pth --gt velodyne [--batch_size 12]
+
+--gt velodyne needs no archive: the ground truth is made from the raw tree's velodyne scans (tripled_amd.velodyne) -- per batch on
+the device by csrc/td_velo.hip with --batch_size N, per frame by KITTIRAWDataset.get_depth in the loop below.
 
 --batch_size N scores N frames per launch chain on the device (tripled_amd.evaluate.DepthEvaluator, csrc/td_eval.hip); the
 default, 0, is the loop below.
@@ -22,20 +26,26 @@ import tripled_amd  # noqa: F401,E402
 from mmcv import Config  # noqa: E402
 from mono.core.evaluation import disp_to_depth, evaluate_disparity  # noqa: E402
 from mono.core.evaluation.eval_hooks import METRICS  # noqa: E402
+from mono.datasets.device_expand import GROUND_TRUTH_KEYS  # noqa: E402
 from mono.datasets.get_dataset import get_dataset  # noqa: E402
 from mono.model import MONO  # noqa: E402
 
 
 def evaluate(model, dataset, stereo_scale=False, device="cuda"):
-    """Returns (mean metrics dict, scale ratios) over a validation dataset whose samples carry 'gt_depth'."""
+    """Returns (mean metrics dict, scale ratios) over a validation dataset whose samples carry 'gt_depth', or (cfg.data.gt_source =
+    'velodyne') a raw scan: the ground truth is then dataset.get_depth of the sample's line."""
     model.eval().to(device)
     results = []
     with torch.no_grad():
         for idx in range(len(dataset)):
             sample = dataset[idx]
-            batch = {k: torch.as_tensor(v).float().unsqueeze(0).to(device) for k, v in sample.items() if k != "gt_depth"}
+            batch = {k: torch.as_tensor(v).float().unsqueeze(0).to(device) for k, v in sample.items() if k not in GROUND_TRUTH_KEYS}
             scaled, _ = disp_to_depth(model(batch)[("disp", 0, 0)].float(), 0.1, 100)
-            gt = np.asarray(sample["gt_depth"], dtype=np.float32)
+            if "gt_depth" in sample:
+                gt = np.asarray(sample["gt_depth"], dtype=np.float32)
+            else:
+                folder, frame_index, side = dataset.filenames[idx].split()
+                gt = dataset.get_depth(folder, int(frame_index), side, False)
             results.append(evaluate_disparity(scaled.cpu()[0, 0].numpy(), gt, stereo_scale))
     mean = {k: float(np.mean([r[k] for r in results])) for k in METRICS}
     return mean, np.array([r["scale"] for r in results])
@@ -53,6 +63,8 @@ def main():
     ap.add_argument("--config", required=True)
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--gt_depths", default=None)
+    ap.add_argument("--gt", choices=("archive", "velodyne"), default=None,
+                    help="where the ground truth comes from (default: cfg.data.gt_source, else the archive); velodyne: the raw scans")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--batch_size", type=int, default=0,
                     help="0: one frame at a time, scored on the host; N > 0: batches of N scored on the device (DepthEvaluator)")
@@ -64,6 +76,8 @@ def main():
     cfg = Config.fromfile(args.config)
     if args.gt_depths:
         cfg.data["gt_depth_path"] = args.gt_depths
+    if args.gt:
+        cfg.data["gt_source"] = args.gt
     cfg.model["imgs_per_gpu"] = 1
     model = MONO.module_dict[cfg.model["name"]](cfg.model)
     ckpt = torch.load(args.checkpoint, map_location="cpu", weights_only=True)      # executes nothing from the file

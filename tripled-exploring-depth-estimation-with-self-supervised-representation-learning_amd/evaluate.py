@@ -207,6 +207,7 @@ class DepthEvaluator:
         self.post_process = bool(post_process)
         self.stereo_scale = bool(stereo_scale)
         self._workspace = None
+        self._velo_workspace = None
 
     def _forward(self, net, batch):
         if self.precision == "bf16":
@@ -214,13 +215,30 @@ class DepthEvaluator:
         with infer.autocast_for(self.precision):
             return net(batch)[("disp", 0, 0)]
 
+    def ground_truth(self, samples):
+        """What score() takes for these samples: their "gt_depth" maps as a list, or, for samples that carry a raw scan instead
+        (cfg.data.gt_source = "velodyne": "velo", "velo_P", "gt_size"), the maps made from the scans -- by td_velo_depth as the padded
+        (gt, sizes, crops) on a HIP device, by the numpy statement as a list on the host."""
+        if "velo" not in samples[0]:
+            return [np.asarray(s["gt_depth"], dtype=np.float32) for s in samples]
+        from . import velodyne
+        if self.on_hip:
+            sizes = np.array([[int(v) for v in s["gt_size"]] for s in samples])
+            need = native.load().td_velo_depth_workspace_bytes(len(samples), int(sizes[:, 0].max()), int(sizes[:, 1].max()))
+            if self._velo_workspace is None or self._velo_workspace.numel() < need:
+                self._velo_workspace = velodyne.velo_workspace(max(len(samples), self.batch_size), sizes[:, 0].max(), sizes[:, 1].max(),
+                                                               self.device)
+        return velodyne.batch_ground_truth([s["velo"] for s in samples], [s["velo_P"] for s in samples],
+                                           [s["gt_size"] for s in samples], self.device, workspace=self._velo_workspace)
+
     def score(self, disp_net, gt_list):
-        """Network disparity [B*(1+post_process),1,h,w] + B ground truths -> ([B,8], [B]) on the device."""
+        """Network disparity [B*(1+post_process),1,h,w] + B ground truths (a list of maps, or the padded (gt, sizes, crops) of
+        ground_truth) -> ([B,8], [B]) on the device."""
         h, w = disp_net.shape[2:]
         if self.on_hip:
             if self.post_process:
                 disp_net = infer.postprocess_hip(disp_net, h, w, paired=True, want_depth=False)[0]
-            gt, sizes, crops = pad_ground_truth(gt_list, self.device)
+            gt, sizes, crops = gt_list if isinstance(gt_list, tuple) else pad_ground_truth(gt_list, self.device)
             need = native.load().td_eval_depth_workspace_bytes(gt.shape[0], gt.shape[1], gt.shape[2])
             if self._workspace is None or self._workspace.numel() < need:
                 self._workspace = eval_workspace(max(gt.shape[0], self.batch_size), gt.shape[1], gt.shape[2], self.device)
@@ -241,7 +259,7 @@ class DepthEvaluator:
         with torch.no_grad(), restore:
             for at in range(0, len(indices), self.batch_size):
                 samples = [dataset[i] for i in indices[at:at + self.batch_size]]
-                gts = [np.asarray(s["gt_depth"], dtype=np.float32) for s in samples]
+                gts = self.ground_truth(samples)
                 batch = collate_validation(samples, self.device)
                 if self.post_process:
                     batch = _with_mirrored(batch)

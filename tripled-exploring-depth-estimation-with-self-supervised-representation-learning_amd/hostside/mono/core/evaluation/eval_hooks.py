@@ -72,7 +72,11 @@ def _predict_one(model, sample):
     with torch.no_grad(), _full_precision(model):
         result = model(batch)
     scaled, _ = disp_to_depth(result[("disp", 0, 0)].float())
-    gt = torch.as_tensor(sample["gt_depth"]).float().cpu().numpy()
+    if "gt_depth" in sample:
+        gt = torch.as_tensor(sample["gt_depth"]).float().cpu().numpy()
+    else:                                      # cfg.data.gt_source = "velodyne": the map of the sample's raw scan
+        from tripled_amd.velodyne import sample_ground_truth
+        gt = sample_ground_truth(sample)
     return scaled.cpu()[0, 0].numpy(), gt
 
 

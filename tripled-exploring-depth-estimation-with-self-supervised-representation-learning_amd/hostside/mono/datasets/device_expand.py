@@ -98,15 +98,19 @@ def expand_device_batch(data):
     return data
 
 
+GROUND_TRUTH_KEYS = ("gt_depth", "velo", "velo_P", "gt_size")      # what a validation sample carries for the scorer alone
+
+
 def collate_validation(samples, device):
     """Validation samples (dataset[i] dicts) -> one network batch on ``device``: what DepthEvaluator and the evaluation hooks feed
     the model.  ("color_u8", f) frames are expanded by the HIP kernel on the device (expand_device_batch) and by plain ToTensor on
-    the host (no jitter in validation).  "gt_depth" stays with the sample (no model reads it) and "aug" is dropped."""
+    the host (no jitter in validation).  "gt_depth" -- or, under gt_source = "velodyne", "velo", "velo_P" and "gt_size" -- stays with
+    the sample (no model reads it) and "aug" is dropped."""
     device = torch.device(device)
     on_hip = device.type == "cuda"
     batch = {}
     for k in samples[0]:
-        if k == "gt_depth":
+        if k in GROUND_TRUTH_KEYS:
             continue
         stacked = torch.stack([torch.as_tensor(s[k]) for s in samples], 0)
         if k in ("raw_spec", "res_bytes"):               # raw_wire.HOST_KEYS: read by the host in the expansion

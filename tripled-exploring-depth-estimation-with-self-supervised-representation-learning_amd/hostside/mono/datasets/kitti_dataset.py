@@ -7,6 +7,11 @@ Sample contract (what the models consume): ("color", f, 0) and ("color_aug", f, 
 [0,1] for every f in frame_idxs, "K" / "inv_K" [4,4] (normalised intrinsics scaled by W, H; inv_K =
 pinv(K)), ("mask", 0, 0) uint8 [3,H,W] for the in-painting variant, "stereo_T" when 's' is a frame id,
 "gt_depth" in validation.  Split lists are plain text: "<folder> <frame_index> <l|r>" per line.
+
+Ground truth of a validation sample (cfg.data.gt_source): "archive" (default) serves "gt_depth" from gt_depth_path, an .npz whose
+"data" is either one [n,H,W] array or, with a "sizes" int32 [n,2] entry next to it, zero-padded maps of different sizes
+(tools/export_gt_depth.py); "velodyne" ships the frame's raw scan instead -- "velo" float32 [N,4], "velo_P" float64 [3,4], "gt_size"
+int32 [2] -- and the evaluation makes the map (tripled_amd.velodyne; KITTIRAWDataset.get_depth is the same map on the host).
 """
 import os
 import random
@@ -94,11 +99,18 @@ class MonoDataset(Dataset):
         self.gt_depth_path = gt_depth_path
         self.flag = np.zeros(len(self), dtype=np.int64)        # single aspect-ratio group for the samplers
         self.gt_depths = None
+        self.gt_sizes = None
         self._raw = None
         self._store_index = None
         if not is_train and gt_depth_path is not None and os.path.exists(str(gt_depth_path)):
             # the reference loads this archive with allow_pickle=True; object arrays are refused here
-            self.gt_depths = np.load(gt_depth_path, allow_pickle=False)["data"]
+            archive = np.load(gt_depth_path, allow_pickle=False)
+            self.gt_depths = archive["data"]
+            if "sizes" in archive.files:      # maps of different sizes, zero-padded to the largest (tools/export_gt_depth.py)
+                self.gt_sizes = np.asarray(archive["sizes"], dtype=np.int64).reshape(-1, 2)
+                if self.gt_depths.ndim != 3 or len(self.gt_sizes) != len(self.gt_depths):
+                    raise ValueError("%s: 'sizes' [n,2] next to 'data' [n,Hmax,Wmax], got %s and %s"
+                                     % (gt_depth_path, self.gt_sizes.shape, self.gt_depths.shape))
 
     def __len__(self):
         return len(self.filenames)
@@ -108,6 +120,9 @@ class MonoDataset(Dataset):
 
     def get_color(self, folder, frame_index, side, do_flip):
         raise NotImplementedError
+
+    def get_velodyne(self, folder, frame_index, side):
+        raise NotImplementedError("cfg.data.gt_source = 'velodyne' needs a dataset with raw scans (KITTIRAWDataset)")
 
     def _raw_layout(self):
         """(sizes, canvas, "raw_spec") of the 'raw_u8' wire format: fixed by the configuration, worked out once."""
@@ -153,7 +168,12 @@ class MonoDataset(Dataset):
         folder = parts[0]
         frame_index = int(parts[1]) if len(parts) == 3 else 0
         side = parts[2] if len(parts) == 3 else None
-        if self.gt_depths is not None:
+        if not self.is_train and self.cfg.get("gt_source", "archive") == "velodyne":
+            inputs.update(self.get_velodyne(folder, frame_index, side))
+        elif self.gt_depths is not None and self.gt_sizes is not None:
+            h, w = self.gt_sizes[index]
+            inputs["gt_depth"] = self.gt_depths[index, :h, :w]
+        elif self.gt_depths is not None:
             inputs["gt_depth"] = self.gt_depths[index]
         jitter = ColorJitter(self.brightness, self.contrast, self.saturation, self.hue) if do_color_aug else None
         # wire = "uint8": frames travel as bytes, ToTensor and the colour jitter run on the device
@@ -246,7 +266,35 @@ class KITTIDataset(MonoDataset):
 
 
 class KITTIRAWDataset(KITTIDataset):
-    pass
+    """KITTI raw with ground truth from the velodyne scans (reference kitti_dataset.py:189-215)."""
+
+    def _calibration(self, folder, side):
+        """(P, (H, W)) of the folder's date and the side's camera, read once per process."""
+        from tripled_amd import velodyne
+        cache = self.__dict__.setdefault("_velo_calib", {})
+        key = (folder.split("/")[0], self.side_map[side])
+        if key not in cache:
+            cache[key] = velodyne.velo_to_image(os.path.join(self.data_path, key[0]), key[1])
+        return cache[key]
+
+    def get_velodyne_path(self, folder, frame_index):
+        return os.path.join(self.data_path, folder, "velodyne_points/data/{:010d}.bin".format(int(frame_index)))
+
+    def get_velodyne(self, folder, frame_index, side):
+        """The three keys of a validation sample under gt_source = 'velodyne'."""
+        from tripled_amd import velodyne
+        P, size = self._calibration(folder, side)
+        return {"velo": torch.from_numpy(velodyne.load_velodyne_points(self.get_velodyne_path(folder, frame_index))),
+                "velo_P": torch.from_numpy(P.copy()), "gt_size": torch.tensor(size, dtype=torch.int32)}
+
+    def get_depth(self, folder, frame_index, side, do_flip):
+        """The reference's method on the host statement: the map at native size, float32, mirrored when flipped.  The reference's
+        scipy.misc.imresize to full_res_shape is left out (it byte-scaled the map; the evaluation reads native size)."""
+        from tripled_amd import velodyne
+        P, (h, w) = self._calibration(folder, side)
+        points = velodyne.load_velodyne_points(self.get_velodyne_path(folder, frame_index))
+        depth_gt = velodyne.depth_map_numpy(points, P, h, w)[0].astype(np.float32)
+        return np.fliplr(depth_gt) if do_flip else depth_gt
 
 
 class KITTIInpaintDataset(KITTIDataset):

@@ -128,6 +128,8 @@ SIGNATURES = {
     "td_cloud_reduce_packed": (_I, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
     "td_cloud_reduce_rows": (_I, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
     "td_cloud_finish": (_I, [_P, _P, ctypes.c_longlong, ctypes.c_double, ctypes.c_longlong, _P, _P, _P, _P, _P]),
+    "td_velo_depth_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
+    "td_velo_depth": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
