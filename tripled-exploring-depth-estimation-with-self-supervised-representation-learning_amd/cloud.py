@@ -288,7 +288,6 @@ def keys_hip(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_vo
              min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=0.0, stats=None):
     """keys_numpy as one launch of td_cloud_keys -> (key int64 [B H W], payload int64 [B H W]: the uint64's bits).  ``stats``: an int64
     [6] device tensor that the launch increments (the order of CAUSES), or None."""
-    lib = native.load()
     native.require_device(depth, color, poses)
     if depth.dtype != torch.float32 or depth.dim() != 3 or color.dtype != torch.uint8 or \
             tuple(color.shape) != (depth.shape[0], 3) + tuple(depth.shape[1:]) or poses.dtype != torch.float64 or \
@@ -305,21 +304,19 @@ def keys_hip(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_vo
     payload = torch.empty(B * H * W, dtype=torch.int64, device=depth.device)
     if B * H * W == 0:                   # an empty tensor has no pointer to pass
         return key, payload
-    native.check(lib.td_cloud_keys(native.ptr(depth.contiguous()), native.ptr(color.contiguous()), native.ptr(poses.contiguous()),
-                                   (ctypes.c_double * 9)(*m), B, H, W, float(depth_scale), float(pose_scale), float(inv_voxel),
-                                   int(stride), int(border), float(min_depth), float(max_range), float(edge), native.ptr(key),
-                                   native.ptr(payload), native.ptr(stats), native.stream()), "td_cloud_keys")
+    native.call("td_cloud_keys", depth.contiguous(), color.contiguous(), poses.contiguous(), (ctypes.c_double * 9)(*m), B, H, W,
+                float(depth_scale), float(pose_scale), float(inv_voxel), int(stride), int(border), float(min_depth), float(max_range),
+                float(edge), key, payload, stats)
     return key, payload
 
 
 def heads_hip(sorted_keys):
     """Sorted int64 keys [N] -> int32 [N]: 1 where a valid key differs from its predecessor (td_cloud_heads)."""
-    lib = native.load()
     keys = _i64(sorted_keys, "sorted_keys")
     flags = torch.empty(keys.shape[0], dtype=torch.int32, device=keys.device)
     if keys.shape[0] == 0:
         return flags
-    native.check(lib.td_cloud_heads(native.ptr(keys), keys.shape[0], native.ptr(flags), native.stream()), "td_cloud_heads")
+    native.call("td_cloud_heads", keys, keys.shape[0], flags)
     return flags
 
 
@@ -327,7 +324,6 @@ def reduce_hip(sorted_keys, seg, perm, src, V):
     """The segmented sum -> (keys int64 [V], sums int64 [V,7]).  ``seg``: torch.cumsum(heads_hip(sorted_keys), 0) (int64, inclusive);
     ``perm``: the sort's permutation or None;  ``src``: int64 [n] payloads as keys_hip wrote them (td_cloud_reduce_packed) or int64
     [n,7] already-summed rows (td_cloud_reduce_rows);  V = seg[-1], which the caller has read."""
-    lib = native.load()
     keys = _i64(sorted_keys, "sorted_keys")
     N, V = keys.shape[0], int(V)
     seg = _i64(seg, "seg", N)
@@ -342,15 +338,13 @@ def reduce_hip(sorted_keys, seg, perm, src, V):
     sums = torch.zeros(V, 7, dtype=torch.int64, device=keys.device)
     if V == 0:
         return out_keys, sums
-    fn, what = (lib.td_cloud_reduce_packed, "td_cloud_reduce_packed") if packed else (lib.td_cloud_reduce_rows, "td_cloud_reduce_rows")
-    native.check(fn(native.ptr(keys), native.ptr(seg), native.ptr(perm), native.ptr(src.contiguous()), src.shape[0], N, V,
-                    native.ptr(out_keys), native.ptr(sums), native.stream()), what)
+    native.call("td_cloud_reduce_packed" if packed else "td_cloud_reduce_rows", keys, seg, perm, src.contiguous(), src.shape[0], N, V,
+                out_keys, sums)
     return out_keys, sums
 
 
 def finish_hip(keys, sums, voxel, min_count=1):
     """finish_numpy as td_cloud_finish -> (xyz float32 [V,3], rgb uint8 [V,3], count int32 [V], keep uint8 [V])."""
-    lib = native.load()
     keys = _i64(keys, "keys")
     V = keys.shape[0]
     native.require_device(sums)
@@ -363,8 +357,7 @@ def finish_hip(keys, sums, voxel, min_count=1):
     count, keep = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.uint8, device=dev)
     if V == 0:
         return xyz, rgb, count, keep
-    native.check(lib.td_cloud_finish(native.ptr(keys), native.ptr(sums.contiguous()), V, float(voxel), int(min_count), native.ptr(xyz),
-                                     native.ptr(rgb), native.ptr(count), native.ptr(keep), native.stream()), "td_cloud_finish")
+    native.call("td_cloud_finish", keys, sums.contiguous(), V, float(voxel), int(min_count), xyz, rgb, count, keep)
     return xyz, rgb, count, keep
 
 

@@ -155,10 +155,8 @@ def evaluate_disparity_hip(disp, gt, sizes, crops, stereo_scale=False, affine=No
         workspace = eval_workspace(B, Hmax, Wmax, disp.device)
     metrics = torch.empty(B, 8, device=disp.device, dtype=torch.float32)
     counts = torch.empty(B, device=disp.device, dtype=torch.int32)
-    native.check(lib.td_eval_depth(native.ptr(disp), native.DTYPE_CODES[disp.dtype], B, h, w, a, b, native.ptr(gt), Hmax, Wmax,
-                                   native.ptr(sizes), native.ptr(crops), min_depth, max_depth, 1 if stereo_scale else 0,
-                                   native.ptr(workspace), workspace.numel() * workspace.element_size(), native.ptr(metrics),
-                                   native.ptr(counts), native.stream()), "td_eval_depth")
+    native.call("td_eval_depth", disp, disp.dtype, B, h, w, a, b, gt, Hmax, Wmax, sizes, crops, min_depth, max_depth, bool(stereo_scale),
+                workspace, workspace.numel() * workspace.element_size(), metrics, counts)
     return metrics, counts
 
 
@@ -174,8 +172,7 @@ def masked_median_hip(values):
     workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=values.device)
     median = torch.empty(B, device=values.device, dtype=torch.float32)
     count = torch.empty(B, device=values.device, dtype=torch.int32)
-    native.check(lib.td_masked_median(native.ptr(values), B, n, native.ptr(workspace), workspace.numel(), native.ptr(median),
-                                      native.ptr(count), native.stream()), "td_masked_median")
+    native.call("td_masked_median", values, B, n, workspace, workspace.numel(), median, count)
     return median, count
 
 

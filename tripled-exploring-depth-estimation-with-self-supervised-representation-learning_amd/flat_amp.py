@@ -261,8 +261,7 @@ class FlatMixedPrecision:
                 g = self._relayout(g, p, dtype)
             keep.append(g)
             srcs[i] = g.data_ptr()
-        native.check(native.load().td_gather_flat(srcs, dst, num, n, native.DTYPE_CODES[dtype], native.ptr(self.flat_g),
-                                                  native.stream()), "td_gather_flat")
+        native.call("td_gather_flat", srcs, dst, num, n, dtype, self.flat_g)
 
     def collect(self):
         """Per-parameter gradients (fresh autograd allocations, bf16 for convolutions / fp32 otherwise) -> the
@@ -322,17 +321,13 @@ class FlatMixedPrecision:
             total = torch.linalg.vector_norm(self.flat_g)
         if self._fused_step_possible():
             from . import native
-            lib = native.load()
             st, grp = self._adam_state(), self.optimizer.param_groups[0]
             st["step"] += 1
             lr = grp["lr"]
-            native.check(lib.td_adam_flat(native.ptr(self.flat_w), native.ptr(self.flat_g), native.ptr(st["exp_avg"]),
-                                          native.ptr(st["exp_avg_sq"]), native.ptr(self.flat_lp) if self.n_lp else None,
-                                          self.flat_w.numel(), self.n_lp, native.ptr(st["step"]),
-                                          native.ptr(lr) if torch.is_tensor(lr) else None, 0.0 if torch.is_tensor(lr) else float(lr),
-                                          float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]),
-                                          native.ptr(total) if total is not None else None,
-                                          float(self.max_norm) if self.max_norm is not None else 0.0, native.stream()), "td_adam_flat")
+            native.call("td_adam_flat", self.flat_w, self.flat_g, st["exp_avg"], st["exp_avg_sq"], self.flat_lp if self.n_lp else None,
+                        self.flat_w.numel(), self.n_lp, st["step"], lr if torch.is_tensor(lr) else None,
+                        0.0 if torch.is_tensor(lr) else float(lr), float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]),
+                        total, float(self.max_norm) if self.max_norm is not None else 0.0)
             return total
         if total is not None:
             self.flat_g.mul_(torch.clamp(self.max_norm / (total + 1e-6), max=1.0))

@@ -129,20 +129,17 @@ def _device_lut(device):
 
 def preprocess_hip(images, height, width, mirror=False):
     """preprocess_torch as one launch of td_infer_preprocess; ``images``: uint8 [B,H0,W0,3] on a HIP device."""
-    lib = native.load()
     native.ptr(images)          # device and contiguous: the input is never copied
     if images.dim() != 4 or images.shape[3] != 3 or images.dtype != torch.uint8:
         raise ValueError("images: uint8 [B,H0,W0,3], got %s %s" % (tuple(images.shape), images.dtype))
     B, H0, W0 = images.shape[:3]
     out = torch.empty(B * (2 if mirror else 1), 3, height, width, device=images.device, dtype=torch.float32)
-    native.check(lib.td_infer_preprocess(native.ptr(images), B, H0, W0, height, width, 1 if mirror else 0, native.ptr(out),
-                                         native.stream()), "td_infer_preprocess")
+    native.call("td_infer_preprocess", images, B, H0, W0, height, width, bool(mirror), out)
     return out
 
 
 def postprocess_hip(disp, out_h, out_w, paired=False, a=None, b=None, depth_scale=1.0, want_depth=True):
     """postprocess_torch as one launch of td_disp_postprocess; ``disp``: fp32 or bf16 [B*(1+paired),1,h,w] on a HIP device."""
-    lib = native.load()
     if a is None or b is None:
         a, b = disp_to_depth_affine(0.1, 100.0)
     if disp.dim() != 4 or disp.shape[1] != 1 or disp.dtype not in native.DTYPE_CODES:
@@ -155,14 +152,12 @@ def postprocess_hip(disp, out_h, out_w, paired=False, a=None, b=None, depth_scal
     h, w = disp.shape[2:]
     d = torch.empty(B, out_h, out_w, device=disp.device, dtype=torch.float32)
     z = torch.empty_like(d) if want_depth else None
-    native.check(lib.td_disp_postprocess(native.ptr(disp), native.DTYPE_CODES[disp.dtype], B, h, w, 1 if paired else 0, out_h, out_w,
-                                         a, b, depth_scale, native.ptr(d), native.ptr(z), native.stream()), "td_disp_postprocess")
+    native.call("td_disp_postprocess", disp, disp.dtype, B, h, w, bool(paired), out_h, out_w, a, b, depth_scale, d, z)
     return d, z
 
 
 def colorize_hip(x, vmin, vmax):
     """colorize_numpy as one launch of td_colorize; x: float32 [B, ...] on a HIP device, vmin / vmax: float32 [B] there."""
-    lib = native.load()
     if x.dtype != torch.float32 or x.dim() < 2:
         raise ValueError("x: float32 [B, ...], got %s %s" % (tuple(x.shape), x.dtype))
     x = x.contiguous()
@@ -171,8 +166,7 @@ def colorize_hip(x, vmin, vmax):
     vmin = vmin.to(torch.float32).reshape(B).contiguous()
     vmax = vmax.to(torch.float32).reshape(B).contiguous()
     out = torch.empty(tuple(x.shape) + (3,), device=x.device, dtype=torch.uint8)
-    native.check(lib.td_colorize(native.ptr(x), B, n, native.ptr(vmin), native.ptr(vmax), native.ptr(_device_lut(x.device)),
-                                 native.ptr(out), native.stream()), "td_colorize")
+    native.call("td_colorize", x, B, n, vmin, vmax, _device_lut(x.device), out)
     return out
 
 

@@ -14,8 +14,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libtripled_hip.so")
 
 TD_MAX_SRC = 4
-_c_float_p = ctypes.c_void_p   # device pointers travel as integers
-_c_u8_p = ctypes.c_void_p
 
 # name -> (restype, argtypes); mirrors include/tripled_hip.h one to one
 _PTRARR = ctypes.POINTER(ctypes.c_void_p)
@@ -203,7 +201,56 @@ def ptr_array(tensors):
 
 
 def stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    """torch's current HIP stream as a hipStream_t.  Asked of the runtime directly: every launch asks (native.call), and
+    torch.cuda.current_stream() builds a Stream object in Python around the same handle each time."""
+    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+
+
+_PLANS = {}      # name -> (arguments in front of the stream, its pointer slots, pointer-array slots, int slots)
+
+
+def _plan(name):
+    slots = SIGNATURES[name][1][:-1]
+    where = lambda kind: tuple(i for i, s in enumerate(slots) if s is kind)
+    plan = _PLANS[name] = (len(slots), where(_P), where(_PTRARR), where(_I))
+    return plan
+
+
+def call(name, *args, what=None):
+    """THE way to launch: ``name`` of SIGNATURES with every argument but the trailing stream, counted by ``check`` as ``what``
+    (default: the name).  Pointer slot: None -> NULL, a tensor -> its device pointer, a ready-made c_void_p (a tensor of another
+    dense layout whose caller checked it) as it is.  Pointer-array slot: a list / tuple of TENSORS (nothing else) -> a host
+    array of their pointers, or a ready-made array.  Every tensor must be on the device (require_device) and dense in planar or
+    channels-last order.  int slot: a torch.dtype -> its DTYPE_CODES entry, a bool -> int.  The other slots (floats, long longs,
+    host arrays) pass as they are.  A wrong argument count is a TypeError -- ctypes itself lets surplus arguments of a cdecl
+    function through.  All of this is checked before the library is loaded or anything is launched.
+    (Only the slots that can need work are visited -- the plan is built once per name: an eager step makes ~850 calls.)"""
+    arity, pointers, arrays, ints = _PLANS.get(name) or _plan(name)
+    if len(args) != arity:
+        raise TypeError("%s takes %d arguments in front of the stream, got %d" % (name, arity, len(args)))
+    conv = list(args)
+    single = [i for i in pointers if conv[i] is not None and type(conv[i]) is not ctypes.c_void_p]
+    lists = [i for i in arrays if type(conv[i]) is list or type(conv[i]) is tuple]
+    tensors = [conv[i] for i in single]
+    for i in lists:
+        tensors.extend(conv[i])
+    try:
+        require_device(*tensors)
+        for t in tensors:
+            if not (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)):
+                raise NativeLibraryError("libtripled_hip needs contiguous tensors")
+    except AttributeError:
+        raise TypeError("%s: a pointer argument is a tensor, None or a c_void_p; a pointer array a list of tensors" % name) from None
+    for i in single:
+        conv[i] = conv[i].data_ptr()
+    for i in lists:
+        conv[i] = (ctypes.c_void_p * len(conv[i]))(*[t.data_ptr() for t in conv[i]])
+    for i in ints:
+        a = conv[i]
+        if type(a) is not int:
+            conv[i] = DTYPE_CODES[a] if type(a) is torch.dtype else int(a)
+    conv.append(stream())
+    check(getattr(load(), name)(*conv), what or name)
 
 
 def strides_array(t):

@@ -221,7 +221,6 @@ def pairs_hip(frames, dtype=torch.float32, first=0, count=None, out=None, out_fi
     """pairs_torch as td_pose_pairs_u8: pairs [first, first+count) of uint8 frames [n+1,3,H,W] as ``dtype`` (fp32 / bf16).
     Without ``out`` a new [count,6,H,W]; with ``out`` [.,6,H,W] the pairs go to its rows out_first ... (default: ``first``, a window
     of the full [n,6,H,W] array; 0 fills a batch buffer) and the other rows are left alone."""
-    lib = native.load()
     native.require_device(frames)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[1] != 3 or frames.shape[0] < 2:
         raise ValueError("frames: uint8 [n+1,3,H,W] with n >= 1, got %s %s" % (tuple(frames.shape), frames.dtype))
@@ -240,32 +239,28 @@ def pairs_hip(frames, dtype=torch.float32, first=0, count=None, out=None, out_fi
                 out_first < 0 or out_first + count > out.shape[0]:
             raise ValueError("out: contiguous %s [>=%d,6,%d,%d], got %s %s" % (dtype, out_first + count, H, W, tuple(out.shape),
                                                                               out.dtype))
-    native.check(lib.td_pose_pairs_u8(native.ptr(frames.contiguous()), n, H, W, int(first), count, native.DTYPE_CODES[dtype],
-                                      native.ptr(out), out_first, native.stream()), "td_pose_pairs_u8")
+    native.call("td_pose_pairs_u8", frames.contiguous(), n, H, W, int(first), count, dtype, out, out_first)
     return out
 
 
 def trajectory_hip(rel, out=None):
     """trajectory_numpy as td_odom_trajectory: rel float32 / float64 [n,4,4] -> float64 [n+1,3,4]."""
-    lib = native.load()
     rel, f64 = _rel(rel)
     n = rel.shape[0]
     out = _out(out, (n + 1, 3, 4), torch.float64, rel.device, "out")
-    native.check(lib.td_odom_trajectory(native.ptr(rel), f64, n, native.ptr(out), native.stream()), "td_odom_trajectory")
+    native.call("td_odom_trajectory", rel, f64, n, out)
     return out
 
 
 def snippet_ates_hip(rel, gt_poses, track_length=TRACK_LENGTH, out=None):
     """snippet_ates_numpy as td_odom_snippet_ate: rel [n,4,4], gt_poses float64 [n+1,3,4] -> float64 [n]."""
-    lib = native.load()
     rel, f64 = _rel(rel)
     n = rel.shape[0]
     gt_poses = _poses(gt_poses, "gt_poses", n + 1)
     if not 2 <= int(track_length) <= 16:
         raise ValueError("track_length: 2 ... 16, got %r" % (track_length,))
     out = _out(out, (n,), torch.float64, rel.device, "out")
-    native.check(lib.td_odom_snippet_ate(native.ptr(rel), f64, native.ptr(gt_poses), n, int(track_length), native.ptr(out),
-                                         native.stream()), "td_odom_snippet_ate")
+    native.call("td_odom_snippet_ate", rel, f64, gt_poses, n, int(track_length), out)
     return out
 
 
@@ -277,7 +272,6 @@ def sequence_errors_hip(gt_poses, pred_poses, lengths=LENGTHS, step=STEP, align_
     """sequence_errors_numpy as td_odom_sequence_errors -> (rows float64 [F,L,5], valid uint8 [F,L], summary float64 [2] = (scale,
     total distance)), F = ceil(m / step) first frames.  A segment that does not fit has valid 0 (and NaN errors), not a zero row;
     ``compact_rows`` drops those on the host."""
-    lib = native.load()
     gt_poses = _poses(gt_poses, "gt_poses")
     m = gt_poses.shape[0]
     pred_poses = _poses(pred_poses, "pred_poses", m)
@@ -290,9 +284,8 @@ def sequence_errors_hip(gt_poses, pred_poses, lengths=LENGTHS, step=STEP, align_
     valid = _out(valid, (F, L), torch.uint8, dev, "valid")
     summary = _out(summary, (2,), torch.float64, dev, "summary")
     dist = torch.empty(m, dtype=torch.float64, device=dev)
-    native.check(lib.td_odom_sequence_errors(native.ptr(gt_poses), native.ptr(pred_poses), m, (ctypes.c_double * L)(*lengths), L,
-                                             int(step), 1 if align_scale else 0, native.ptr(dist), native.ptr(rows),
-                                             native.ptr(valid), native.ptr(summary), native.stream()), "td_odom_sequence_errors")
+    native.call("td_odom_sequence_errors", gt_poses, pred_poses, m, (ctypes.c_double * L)(*lengths), L, int(step), bool(align_scale),
+                dist, rows, valid, summary)
     return rows, valid, summary
 
 
@@ -358,7 +351,6 @@ class OdometryEvaluator:
                     axisangle, translation = self._pose_vectors(net, pairs[at:at + self.batch_size])
                     out.append(net.transformation_from_parameters(axisangle, translation, invert=False))
                 return torch.cat(out, 0)
-            lib = native.load()
             resident = frames.to(self.device)                                  # every frame: one upload, as bytes
             rel = torch.empty(n, 4, 4, dtype=torch.float32, device=self.device)
             batch = torch.empty(min(self.batch_size, n), 6, frames.shape[2], frames.shape[3], dtype=torch.float32, device=self.device)
@@ -368,8 +360,7 @@ class OdometryEvaluator:
                 pairs_hip(resident, torch.float32, at, count, out=batch, out_first=0)
                 axisangle, translation = self._pose_vectors(net, batch[:count])
                 axisangle, translation = axisangle.reshape(count, 3).contiguous(), translation.reshape(count, 3).contiguous()
-                native.check(lib.td_pose_fwd(native.ptr(axisangle), native.ptr(translation), no_invert, None, 1, count,
-                                             native.ptr(rel[at:at + count]), None, native.stream()), "td_pose_fwd")
+                native.call("td_pose_fwd", axisangle, translation, no_invert, None, 1, count, rel[at:at + count], None)
             return rel
 
     def evaluate(self, dataset, gt_poses, track_length=TRACK_LENGTH, lengths=LENGTHS, step=STEP, relative=None):

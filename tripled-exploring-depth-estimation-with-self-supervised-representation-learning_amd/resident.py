@@ -302,7 +302,6 @@ def resize_from_store_hip(store, offsets, meta, bank):
     resize.check_banks reports it).  Host offsets / meta are checked by the entry point (TD_ERR_BAD_ARG) and uploaded -- the eager /
     test form."""
     from . import native
-    lib = native.load()
     data = store.data if isinstance(store, ResidentStore) else store
     if not torch.is_tensor(data) or data.dtype != torch.uint8 or data.dim() != 1:
         raise ValueError("store must be a ResidentStore or a 1-D uint8 tensor")
@@ -328,10 +327,8 @@ def resize_from_store_hip(store, offsets, meta, bank):
     offsets, meta = offsets.contiguous(), meta.contiguous()
     out = torch.empty(N, 3, bank.out_h, bank.out_w, dtype=torch.uint8, device=data.device)
     desc = bank.desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    native.check(lib.td_lanczos_resize_u8_indexed(native.ptr(data), int(data.numel()), native.ptr(offsets), offsets_host, native.ptr(meta),
-                                                  meta_host, native.ptr(bank.tables), int(bank.tables.numel()), desc, len(bank.sizes), N,
-                                                  bank.out_h, bank.out_w, native.ptr(out), native.ptr(bank.status), native.stream()),
-                 "td_lanczos_resize_u8_indexed")
+    native.call("td_lanczos_resize_u8_indexed", data, int(data.numel()), offsets, offsets_host, meta, meta_host, bank.tables,
+                int(bank.tables.numel()), desc, len(bank.sizes), N, bank.out_h, bank.out_w, out, bank.status)
     return out
 
 

@@ -213,7 +213,6 @@ def lanczos_resize_hip(frames, meta, bank):
     A ``meta`` on the device is not read by the host (graph capture): an index outside the bank zero-fills that image and raises
     ``bank.status``.  A ``meta`` on the host is checked by the entry point (TD_ERR_BAD_ARG) and uploaded -- the eager / test form."""
     from . import native
-    lib = native.load()
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[1] != 3:
         raise ValueError("frames must be uint8 [N,3,Hc,Wc]")
     if not frames.is_cuda:
@@ -233,7 +232,6 @@ def lanczos_resize_hip(frames, meta, bank):
     meta = meta.contiguous()
     out = torch.empty(N, 3, bank.out_h, bank.out_w, dtype=torch.uint8, device=frames.device)
     desc = bank.desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-    native.check(lib.td_lanczos_resize_u8(native.ptr(frames), native.ptr(meta), meta_host, native.ptr(bank.tables),
-                                          int(bank.tables.numel()), desc, len(bank.sizes), N, Hc, Wc, bank.out_h, bank.out_w,
-                                          native.ptr(out), native.ptr(bank.status), native.stream()), "td_lanczos_resize_u8")
+    native.call("td_lanczos_resize_u8", frames, meta, meta_host, bank.tables, int(bank.tables.numel()), desc, len(bank.sizes), N, Hc, Wc,
+                bank.out_h, bank.out_w, out, bank.status)
     return out

@@ -238,9 +238,7 @@ def depth_maps_hip(points, offsets, P, sizes, vel_depth=False, workspace=None, m
         points = torch.zeros(1, 4, dtype=torch.float32, device=points.device)
     gt = torch.empty(B, Hmax, Wmax, dtype=torch.float32, device=points.device)
     stats = torch.empty(B, 6, dtype=torch.int64, device=points.device)
-    native.check(lib.td_velo_depth(native.ptr(points), native.ptr(offsets), B, native.ptr(P), native.ptr(sizes), Hmax, Wmax,
-                                   1 if vel_depth else 0, native.ptr(workspace), have, native.ptr(gt), native.ptr(stats),
-                                   native.stream()), "td_velo_depth")
+    native.call("td_velo_depth", points, offsets, B, P, sizes, Hmax, Wmax, bool(vel_depth), workspace, have, gt, stats)
     return gt, stats
 
 
