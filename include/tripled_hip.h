@@ -777,6 +777,38 @@ int td_cloud_finish(const long long* keys, const long long* sums, long long V, d
                     uint8_t* rgb, int* count, uint8_t* keep, td_stream_t stream);
 
 /*
+ * Multi-view consistency of a sequence's depth maps (csrc/td_views.hip).  The reference has no such program: the statement is
+ * tripled_amd/cloud.py:views_numpy, which the kernel equals bit for bit.  For every pixel of the centre frames c0 ... c1-1, the
+ * number of neighbouring frames that, reprojected, see the same depth there.  One launch, plain stores, no synchronisation.
+ *
+ * td_cloud_views.  depth [N,H,W] float32, the whole window;  poses [N,3,4] float64, camera-to-world (device);  K, inv_K: HOST arrays,
+ *   the nine float64 entries of the 3x3 blocks.  The neighbours of centre i are the 2 radius other frames of a .. a + 2 radius,
+ *   a = min(max(i - radius, lo), hi - 1 - 2 radius): the window is shifted, not shortened, at the ends of [lo, hi).
+ *   float64 throughout, every product, sum and quotient rounded on its own (R, t: a pose's rotation and translation):
+ *     ok_f = isfinite(d_f) and min_depth <= ds_f <= max_range,  ds_f = (double)d_f depth_scale
+ *     ray_k = (m_k0 u + m_k1 v) + m_k2;  p = ds_i ray;  w_k = ((Ri_k0 p_x + Ri_k1 p_y) + Ri_k2 p_z) + pose_scale ti_k    (td_cloud_keys)
+ *     e_k = w_k - pose_scale tj_k;  q_k = (Rj_0k e_0 + Rj_1k e_1) + Rj_2k e_2;  z = q_2
+ *     X = (K00 q_0 + K01 q_1) + K02 q_2;  Y = (K10 q_0 + K11 q_1) + K12 q_2;  uj = X / z;  vj = Y / z
+ *     inside = ok_i and z > 0 and 0 <= uj <= W-1 and 0 <= vj <= H-1     (a NaN fails)
+ *     x0 = min(floor(uj), W-2);  y0 = min(floor(vj), H-2);  fx = uj - x0;  fy = vj - y0
+ *     t00, t01, t10, t11 = ds_j at (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1), all four ok_j
+ *     top = t00 + fx (t01 - t00);  bot = t10 + fx (t11 - t10);  s = top + fy (bot - top)
+ *     neighbour j votes when inside, the taps are ok and |z - s| <= tol min(z, s)
+ *   key, payload [(c1-c0) H W] (in/out, td_cloud_keys' pairs of the centre frames) or both NULL.  With key: a pixel whose key is
+ *     INT64_MAX is skipped (0 votes, not tested); a tested pixel with fewer than min_views votes gets key INT64_MAX and payload 0.
+ *     Without key every pixel is tested and nothing but votes is written.
+ *   votes [(c1-c0) H W] uint8 (out) or NULL (only with key);  stats [2] int64 (device) or NULL: incremented by the numbers of pixels
+ *     tested and of tested pixels with fewer than min_views votes.
+ *   TD_ERR_BAD_ARG before any launch: a null depth, poses, K or inv_K, key without payload or payload without key, neither key nor
+ *     votes, N < 0, H < 2, W < 2, radius outside 1..8, min_views outside 0 .. 2 radius, tol negative or NaN, not 0 <= lo <= c0 <=
+ *     c1 <= hi <= N, hi - lo < 2 radius + 1.  N = 0 or c0 = c1 is a successful no-op without a launch (checked before the window's
+ *     length).  TD_ERR_UNSUPPORTED: a frame of more than 2^29 pixels (offsets inside a frame are 32-bit).
+ */
+int td_cloud_views(const float* depth, const double* poses, const double* K, const double* inv_K, int N, int H, int W, int c0, int c1,
+                   int lo, int hi, int radius, int min_views, double tol, double depth_scale, double pose_scale, double min_depth,
+                   double max_range, long long* key, unsigned long long* payload, uint8_t* votes, long long* stats, td_stream_t stream);
+
+/*
  * KITTI ground-truth depth maps from velodyne scans, a batch of frames of different sizes per call (csrc/td_velo.hip,
  * tripled_amd/velodyne.py).  Replaces generate_depth_map, mono/datasets/kitti_utils.py:50-102 (the projection :71-86, the last-write
  * scatter :89-90, the duplicate rule with sub2ind :43-47,93-99, the clamp :100), which KITTIRAWDataset.get_depth calls per frame,

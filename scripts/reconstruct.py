@@ -4,13 +4,18 @@ voxel-averaged coloured point cloud (binary PLY: x y z float, red green blue uch
 
   python scripts/reconstruct.py --config config/cfg_kitti_tripleD.py --checkpoint work/epoch_20.pth --data_path /data/kitti_odom \
          --sequence 9 [--frames A:B] [--poses FILE] [--voxel V] [--stride S] [--border P] [--max_range R] [--edge E] [--min_count N] \
-         [--depth_scale S] [--pose_scale S] [--batch_size 12] [--precision bf16] [--post_process] [--device cpu] --out cloud.ply
+         [--min_views M] [--view_radius R] [--view_tol T] [--depth_scale S] [--pose_scale S] [--batch_size 12] [--precision bf16] \
+         [--post_process] [--device cpu] --out cloud.ply
 
 Frames: <data_path>/sequences/NN/image_0/%06d.png; the frame count is the line count of <data_path>/poses/NN.txt (or of --poses).
 Without --poses the model's own poses are used (depth and pose share the model's scale); --poses FILE takes camera-to-world poses
 in KITTI pose text (the ground truth: give --depth_scale, the model's unit in metres, ~36 for a stereo-trained checkpoint).
---voxel, --max_range and --edge are in the model's units; their defaults are untuned starting values.  The work is
-tripled_amd.cloud.SceneFuser (csrc/td_cloud.hip on a HIP device); the last line printed is the statistics.
+--voxel, --max_range and --edge are in the model's units; their defaults are untuned starting values.  --min_views M (default 0: off)
+keeps a pixel only if at least M of the 2 R frames around its own (--view_radius R) see a depth within --view_tol of its own where
+the pixel's point projects into them; the defaults of R and T are untuned as well.  With it the statistics gain invalid_views, and
+the last line is the consistency rate, the kept pixels over the tested ones: a figure of a checkpoint that needs no ground truth.
+The work is tripled_amd.cloud.SceneFuser (csrc/td_cloud.hip and csrc/td_views.hip on a HIP device); without --min_views the last
+line printed is the statistics.
 """
 import argparse
 import os
@@ -45,6 +50,9 @@ def main():
     ap.add_argument("--max_range", type=float, default=cloud.DEFAULT_MAX_RANGE)
     ap.add_argument("--edge", type=float, default=cloud.DEFAULT_EDGE)
     ap.add_argument("--min_count", type=int, default=1)
+    ap.add_argument("--min_views", type=int, default=0, help="multi-view filter: neighbouring frames that must confirm a pixel (0: off)")
+    ap.add_argument("--view_radius", type=int, default=cloud.DEFAULT_VIEW_RADIUS, help="frames on either side that are asked (untuned)")
+    ap.add_argument("--view_tol", type=float, default=cloud.DEFAULT_VIEW_TOL, help="relative depth difference that still agrees (untuned)")
     ap.add_argument("--depth_scale", type=float, default=1.0)
     ap.add_argument("--pose_scale", type=float, default=1.0)
     ap.add_argument("--batch_size", type=int, default=12)
@@ -72,13 +80,17 @@ def main():
     fuser = cloud.SceneFuser(model, height, width, args.device, voxel=args.voxel, batch_size=args.batch_size, precision=args.precision,
                              stride=args.stride, border=args.border, min_depth=args.min_depth, max_range=args.max_range, edge=args.edge,
                              min_count=args.min_count, depth_scale=args.depth_scale, pose_scale=args.pose_scale,
-                             post_process=args.post_process)
+                             post_process=args.post_process, min_views=args.min_views, view_radius=args.view_radius,
+                             view_tol=args.view_tol)
     print("-> Fusing sequence %02d: frames %s of %d" % (args.sequence, "%d:%d" % frames if frames else "0:%d" % n_frames, n_frames))
     result = fuser.fuse(dataset, poses=poses, frames=frames)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     cloud.save_ply(args.out, result.xyz, result.rgb, result.count)
     print("saved %d points to %s" % (len(result.keys), args.out))
     print(" ".join("%s %d" % (k, v) for k, v in result.stats.items()))
+    if args.min_views:
+        kept, tested = result.stats["valid"], result.stats["valid"] + result.stats["invalid_views"]
+        print("consistency rate %.4f (%d of %d tested pixels have %d views or more)" % (kept / max(tested, 1), kept, tested, args.min_views))
 
 
 if __name__ == "__main__":

@@ -10,11 +10,19 @@ voxel.  Timed separately, with device events, median of ``--repeats`` after ``--
   table       td_cloud_heads, torch.cumsum, td_cloud_reduce_packed, with the voxel count known (no synchronisation inside)
   merge       merge_hip of the chunk's voxels into a running map built from ``--map_chunks`` earlier chunks of the same drive
   chunk       everything a chunk costs after the depth network: keys, table_hip, merge_hip, host clock around a synchronise
+The multi-view filter (csrc/td_views.hip; ``--view_radius``, ``--view_tol``, ``--min_views``, which must be > 0 here), with the chunk's
+own 12 frames as the window (every frame a centre, every frame a possible neighbour):
+  views          td_cloud_views without keys: every pixel is tested and the votes are written (its upper bound)
+  views_on_keys  td_cloud_views on the pairs td_cloud_keys wrote (fresh copies per run, made outside the timed window): pixels that
+                 are invalid already are skipped, the others are tested, pixels with fewer than min_views votes lose their key
+  chunk_views    the chunk with the filter on: keys, views on those keys, table_hip, merge_hip; ``chunk`` is the filter off, the
+                 launches of a build without the filter
 Alongside: the numpy statement's time for the same batch (keys_numpy + voxel_table_numpy, once), and the number of host
 synchronisations per chunk, counted as the Tensor.item() calls of one chunk.  The network, the frame upload and the per-batch
 permuted copy of the frames that DepthPredictor wants are not part of this benchmark.
 
-  python tools/cloud_bench.py [--repeats 20] [--warmup 3] [--map_chunks 8] [--json profiles/cloud/cloud_bench.json]
+  python tools/cloud_bench.py [--repeats 20] [--warmup 3] [--map_chunks 8] [--min_views 2] [--view_radius 2] [--view_tol 0.05]
+                              [--json profiles/cloud/cloud_bench.json]
 """
 import argparse
 import json
@@ -52,21 +60,26 @@ def chunk_inputs(index, H, W, device):
     return depth.to(device), color.to(device), torch.from_numpy(poses).to(device)
 
 
+def intrinsics(H, W):
+    return np.array([[0.58 * W, 0, 0.5 * W], [0, 1.92 * H, 0.5 * H], [0, 0, 1]], dtype=np.float64)
+
+
 def inv_K(H, W):
-    K = np.array([[0.58 * W, 0, 0.5 * W], [0, 1.92 * H, 0.5 * H], [0, 0, 1]], dtype=np.float64)
-    return np.linalg.inv(K)
+    return np.linalg.inv(intrinsics(H, W))
 
 
-def timed(fn, warmup, repeats):
-    """Median, minimum and maximum of ``repeats`` device-event timings of fn(), in microseconds."""
+def timed(fn, warmup, repeats, setup=None):
+    """Median, minimum and maximum of ``repeats`` device-event timings of fn(*setup()), in microseconds; ``setup`` runs outside the
+    timed window."""
     for _ in range(warmup):
-        fn()
+        fn(*(setup() if setup else ()))
     torch.cuda.synchronize()
     out = []
     for _ in range(repeats):
+        given = setup() if setup else ()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        fn()
+        fn(*given)
         b.record()
         b.synchronize()
         out.append(a.elapsed_time(b) * 1e3)
@@ -87,6 +100,20 @@ def count_items(fn):
     finally:
         torch.Tensor.item = item
     return calls[0]
+
+
+def wall_clock(fn, args):
+    """Median, minimum and maximum of the host clock around fn() and a synchronise, in microseconds."""
+    for _ in range(args.warmup):
+        fn()
+    wall = []
+    for _ in range(args.repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e6)
+    return {"median_us": statistics.median(wall), "min_us": min(wall), "max_us": max(wall)}
 
 
 def bench_size(H, W, device, args):
@@ -114,21 +141,31 @@ def bench_size(H, W, device, args):
         k, p = cloud.keys_hip(depth, color, poses, ik, **PARAMS)
         cloud.merge_hip(vmap_keys, vmap_sums, *cloud.table_hip(k, p))
 
+    K = intrinsics(H, W)
+    view = dict(radius=args.view_radius, tol=args.view_tol, depth_scale=PARAMS["depth_scale"], pose_scale=PARAMS["pose_scale"],
+                min_depth=PARAMS["min_depth"], max_range=PARAMS["max_range"])
+
+    def views_on_keys(k, p):
+        cloud.views_hip(depth, poses, ik, K, key=k, payload=p, min_views=args.min_views, votes=False, **view)
+
+    def chunk_views():
+        k, p = cloud.keys_hip(depth, color, poses, ik, **PARAMS)
+        views_on_keys(k, p)
+        cloud.merge_hip(vmap_keys, vmap_sums, *cloud.table_hip(k, p))
+
     out["keys"] = timed(lambda: cloud.keys_hip(depth, color, poses, ik, **PARAMS), args.warmup, args.repeats)
+    out["views"] = timed(lambda: cloud.views_hip(depth, poses, ik, K, **view), args.warmup, args.repeats)
+    out["views_on_keys"] = timed(views_on_keys, args.warmup, args.repeats, setup=lambda: (key.clone(), payload.clone()))
+    counts = torch.zeros(2, dtype=torch.int64, device=device)
+    cloud.views_hip(depth, poses, ik, K, key=key.clone(), payload=payload.clone(), min_views=args.min_views, stats=counts, votes=False, **view)
+    out["views_tested"], out["views_dropped"] = (int(v) for v in counts.cpu())
     out["sort"] = timed(lambda: torch.sort(key), args.warmup, args.repeats)
     out["table"] = timed(table, args.warmup, args.repeats)
     out["merge"] = timed(lambda: cloud.merge_hip(vmap_keys, vmap_sums, ckeys, csums), args.warmup, args.repeats)
-    for _ in range(args.warmup):
-        chunk()
-    wall = []
-    for _ in range(args.repeats):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        chunk()
-        torch.cuda.synchronize()
-        wall.append((time.perf_counter() - t0) * 1e6)
-    out["chunk"] = {"median_us": statistics.median(wall), "min_us": min(wall), "max_us": max(wall)}
+    out["chunk"] = wall_clock(chunk, args)
     out["host_syncs_per_chunk"] = count_items(chunk)
+    out["chunk_views"] = wall_clock(chunk_views, args)
+    out["host_syncs_per_chunk_views"] = count_items(chunk_views)
     rate = 23.0 * n / (out["keys"]["median_us"] * 1e-6)
     out["keys_bytes_per_s"] = rate
     out["keys_fraction_of_hbm_spec"], out["keys_fraction_of_measured_copy"] = rate / HBM_SPEC, rate / HBM_COPY
@@ -140,6 +177,10 @@ def bench_size(H, W, device, args):
     t2 = time.perf_counter()
     out["numpy_keys_s"], out["numpy_table_s"] = t1 - t0, t2 - t1
     out["device_equals_numpy"] = bool(np.array_equal(ckeys.cpu().numpy(), hkeys) and np.array_equal(csums.cpu().numpy(), hsums))
+    t0 = time.perf_counter()
+    hvotes = cloud.views_numpy(d, p, ik, K, **view)
+    out["numpy_views_s"] = time.perf_counter() - t0
+    out["views_equal_numpy"] = bool(np.array_equal(cloud.views_hip(depth, poses, ik, K, **view).cpu().numpy(), hvotes))
     return out
 
 
@@ -148,10 +189,16 @@ def main():
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--map_chunks", type=int, default=8)
+    ap.add_argument("--min_views", type=int, default=2)
+    ap.add_argument("--view_radius", type=int, default=cloud.DEFAULT_VIEW_RADIUS)
+    ap.add_argument("--view_tol", type=float, default=cloud.DEFAULT_VIEW_TOL)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.min_views < 1:
+        ap.error("--min_views: at least 1 (the chunk without the filter is timed as well)")
     device = torch.device("cuda", 0)
     out = {"device": torch.cuda.get_device_name(0), "voxel": VOXEL, "repeats": args.repeats, "warmup": args.warmup,
+           "min_views": args.min_views, "view_radius": args.view_radius, "view_tol": args.view_tol,
            "sizes": [bench_size(H, W, device, args) for H, W in ((192, 640), (320, 1024))]}
     line = json.dumps(out)
     print(line)

@@ -15,8 +15,8 @@ Three layers, as in odometry.py:
   * host statements in numpy (``keys_numpy``, ``voxel_table_numpy``, ``finish_numpy``, ``fuse_numpy``, ``pack_key`` / ``unpack_key``,
     ``save_ply`` / ``load_ply``): the host path (``device='cpu'``) and what the kernels are tested against.  The arithmetic is written
     element-wise in the kernel's operation order: no ``@`` and no einsum, which BLAS may fuse;
-  * ``keys_hip``, ``heads_hip``, ``reduce_hip``, ``finish_hip``, ``merge_hip`` (and ``table_hip`` / ``fuse_hip``, which chain them):
-    device tensors only, a CPU tensor is an error; the kernels themselves never synchronise;
+  * ``keys_hip``, ``views_hip``, ``heads_hip``, ``reduce_hip``, ``finish_hip``, ``merge_hip`` (and ``table_hip`` / ``fuse_hip``, which
+    chain them): device tensors only, a CPU tensor is an error; the kernels themselves never synchronise;
   * ``SceneFuser``: frames of a dataset -> DepthPredictor + OdometryEvaluator.relative_poses / trajectory_hip -> the cloud.
 
 The exact arithmetic (float64; every product and sum rounded on its own; pixel (u, v) at integer coordinates like the reference's
@@ -27,6 +27,22 @@ Backproject, no half-pixel offset):
     g = world inv_voxel;  i = floor(g);  q = min(1023, int(floor((g - i) 1024.0)))
     key = ((i_x + 2^20) << 42) | ((i_y + 2^20) << 21) | (i_z + 2^20);  payload = q_x | q_y << 10 | q_z << 20 | r << 30 | g << 38 | b << 46
     voxel:  xyz = float32((i + (sum q / count + 0.5) / 1024.0) voxel);  rgb = (2 sum c + count) // (2 count)
+
+The multi-view filter (``min_views`` > 0; ``views_numpy`` is its statement, csrc/td_views.hip its kernel) keeps a pixel only if enough
+neighbouring frames, reprojected, see the same depth there: what single-frame filters cannot catch (moving objects, sky, scale drift
+between frames, smeared boundaries) disagrees between views.  The neighbours of frame i are the 2 radius other frames of the window
+a .. a + 2 radius, a = min(max(i - radius, lo), hi - 1 - 2 radius): shifted, not shortened, at the ends of the sequence.  Per pixel of
+frame i and neighbour j, float64, every product, sum and quotient rounded on its own (R, t: a pose's rotation and translation; K's
+3x3 block):
+    ok_f   = isfinite(d_f) and min_depth <= ds_f <= max_range,   ds_f = float64(d_f) depth_scale
+    p, w   = the camera point and the world point of the pixel, as above (p = ds_i ray, w = world)
+    e_k    = w_k - pose_scale tj_k;   q_k = (Rj_0k e_0 + Rj_1k e_1) + Rj_2k e_2       (the transpose of Rj: the stated inverse)
+    z = q_2;  X = (K00 q_0 + K01 q_1) + K02 q_2;  Y = (K10 q_0 + K11 q_1) + K12 q_2;  uj = X / z;  vj = Y / z
+    inside = ok_i and z > 0 and 0 <= uj <= W-1 and 0 <= vj <= H-1                     (a NaN fails)
+    x0 = min(floor(uj), W-2);  y0 = min(floor(vj), H-2);  fx = uj - x0;  fy = vj - y0
+    t00, t01, t10, t11 = ds_j at (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1);  all four must be ok_j
+    top = t00 + fx (t01 - t00);  bot = t10 + fx (t11 - t10);  s = top + fy (bot - top)
+    vote   = inside and the taps are ok and |z - s| <= tol min(z, s)
 """
 import collections
 import ctypes
@@ -46,11 +62,15 @@ DEFAULT_VOXEL = 0.005        # ~0.18 m
 DEFAULT_MIN_DEPTH = 0.1      # the depth network's own lower limit (disp_to_depth)
 DEFAULT_MAX_RANGE = 1.0      # ~36 m: monocular depth degrades with range
 DEFAULT_EDGE = 0.1           # 10 % depth step to a 4-neighbour
+DEFAULT_VIEW_RADIUS = 2      # the multi-view filter (off by default: min_views = 0) asks the 2 frames before and the 2 after; UNTUNED
+DEFAULT_VIEW_TOL = 0.05      # 5 % of the smaller of the two depths; UNTUNED like the rest
+MAX_VIEW_RADIUS = 8          # csrc/td_views.hip: TD_VIEWS_MAX_RADIUS
 
 Cloud = collections.namedtuple("Cloud", "xyz rgb count keys stats")
 Cloud.__doc__ = """xyz float32 [V,3], rgb uint8 [V,3], count int32 [V] (points fused into the voxel, saturating), keys int64 [V] (ascending:
 the output order is defined), on the fuser's device (numpy arrays on the host path);  stats: dict of Python ints: points (pixels
-seen), valid, invalid_stride / _border / _depth / _edge / _range (by the first cause that holds), voxels (before min_count),
+seen), valid, invalid_stride / _border / _depth / _edge / _range (by the first cause that holds), with min_views > 0 invalid_views
+(pixels valid by all of those that too few neighbouring frames confirm; ``valid`` is what is left), voxels (before min_count),
 voxels_dropped (by min_count)."""
 
 PLY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"), ("count", "<i4")])
@@ -93,14 +113,41 @@ def _check_params(voxel, stride, border, min_depth, max_range, edge, min_count=1
         raise ValueError("edge >= 0 and min_depth <= max_range; got %r, %r, %r" % (edge, min_depth, max_range))
 
 
-def _inv_K9(inv_K):
+def _check_view_params(min_views, view_radius, view_tol):
+    if not 1 <= int(view_radius) <= MAX_VIEW_RADIUS or not view_tol >= 0:
+        raise ValueError("view_radius: 1 ... %d, view_tol >= 0; got %r, %r" % (MAX_VIEW_RADIUS, view_radius, view_tol))
+    if not 0 <= int(min_views) <= 2 * int(view_radius):
+        raise ValueError("min_views: 0 ... 2 view_radius = %d (a frame has that many neighbours), got %r" % (2 * int(view_radius), min_views))
+
+
+def _inv_K9(inv_K, name="inv_K"):
     m = np.asarray(inv_K, dtype=np.float64)
     if m.shape in ((3, 3), (4, 4)):
         m = m[:3, :3]
     m = np.ascontiguousarray(m).reshape(-1)
     if m.shape != (9,):
-        raise ValueError("inv_K: 3x3 (or 4x4, whose 3x3 block is used), got %s" % (np.shape(inv_K),))
+        raise ValueError("%s: 3x3 (or 4x4, whose 3x3 block is used), got %s" % (name, np.shape(inv_K)))
     return m
+
+
+def _view_K9(K, inv_K):
+    """The nine entries of K's 3x3 block; ``K`` None: the float64 inverse of inv_K's."""
+    return _inv_K9(np.linalg.inv(_inv_K9(inv_K).reshape(3, 3)) if K is None else K, "K")
+
+
+def _view_ranges(N, H, W, radius, tol, centres, bounds):
+    """The checked (radius, c0, c1, lo, hi) of views_numpy / views_hip."""
+    if H < 2 or W < 2:
+        raise ValueError("frames of at least 2 x 2 pixels (the four taps), got %d x %d" % (H, W))
+    if not 1 <= int(radius) <= MAX_VIEW_RADIUS or not tol >= 0:
+        raise ValueError("radius: 1 ... %d, tol >= 0; got %r, %r" % (MAX_VIEW_RADIUS, radius, tol))
+    lo, hi = (0, N) if bounds is None else (int(bounds[0]), int(bounds[1]))
+    c0, c1 = (lo, hi) if centres is None else (int(centres[0]), int(centres[1]))
+    if not 0 <= lo <= c0 <= c1 <= hi <= N:
+        raise ValueError("0 <= lo <= c0 <= c1 <= hi <= %d; got centres %r, bounds %r" % (N, centres, bounds))
+    if hi - lo < 2 * int(radius) + 1:
+        raise ValueError("radius %d needs %d frames, the bounds hold %d" % (radius, 2 * int(radius) + 1, hi - lo))
+    return int(radius), c0, c1, lo, hi
 
 
 def camera_points_numpy(depth, inv_K, depth_scale=1.0):
@@ -176,6 +223,65 @@ def keys_numpy(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_
     return key, payload, np.bincount(cause.reshape(-1), minlength=6).astype(np.int64)
 
 
+def views_numpy(depth, poses, inv_K, K, radius, tol, depth_scale=1.0, pose_scale=1.0, min_depth=DEFAULT_MIN_DEPTH,
+                max_range=DEFAULT_MAX_RANGE, centres=None, bounds=None):
+    """depth float32 [N,H,W], poses float64 [N,3,4] camera-to-world, K / inv_K: the 3x3 blocks -> votes uint8 [c1-c0,H,W]: for every
+    pixel of the frames ``centres`` = (c0, c1) (default: the frames of ``bounds``) the number of its 2 radius neighbours inside
+    ``bounds`` = (lo, hi) (default: (0, N)) that see the same depth there; 0 where the pixel's own depth is not ok.  The statement
+    td_cloud_views is tested against, operation for operation (the module's docstring).
+
+    A depth test alone is enough: the neighbour's surface is sampled where the pixel's point projects, so where z and s agree the
+    point the neighbour sees there, sent back into frame i, lands within the same relative difference of the pixel it came from:
+    the round-trip reprojection error is bounded by the difference that is tested, and a second criterion would add nothing."""
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    if d.ndim != 3 or P.shape != (d.shape[0], 3, 4):
+        raise ValueError("depth [N,H,W], poses [N,3,4]; got %s, %s" % (d.shape, P.shape))
+    N, H, W = d.shape
+    radius, c0, c1, lo, hi = _view_ranges(N, H, W, radius, tol, centres, bounds)
+    m, k = _inv_K9(inv_K), _inv_K9(K, "K")
+    depth_scale, pose_scale, tol = np.float64(depth_scale), np.float64(pose_scale), np.float64(tol)
+    votes = np.zeros((c1 - c0, H, W), np.uint8)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        ds = d.astype(np.float64) * depth_scale
+        ok = np.isfinite(d) & (ds >= np.float64(min_depth)) & (ds <= np.float64(max_range))
+        for i in range(c0, c1):
+            p = camera_points_numpy(d[i:i + 1], m, depth_scale)[:, 0]
+            w = [((P[i, r, 0] * p[0] + P[i, r, 1] * p[1]) + P[i, r, 2] * p[2]) + pose_scale * P[i, r, 3] for r in range(3)]
+            first = min(max(i - radius, lo), hi - 1 - 2 * radius)
+            for j in range(first, first + 2 * radius + 1):
+                if j == i:
+                    continue
+                e = [w[r] - pose_scale * P[j, r, 3] for r in range(3)]
+                q = [(P[j, 0, r] * e[0] + P[j, 1, r] * e[1]) + P[j, 2, r] * e[2] for r in range(3)]
+                z = q[2]
+                uj = ((k[0] * q[0] + k[1] * q[1]) + k[2] * q[2]) / z
+                vj = ((k[3] * q[0] + k[4] * q[1]) + k[5] * q[2]) / z
+                inside = ok[i] & (z > 0) & (uj >= 0) & (uj <= W - 1) & (vj >= 0) & (vj <= H - 1)          # a NaN fails
+                x0 = np.minimum(np.floor(np.where(inside, uj, 0.0)), W - 2)
+                y0 = np.minimum(np.floor(np.where(inside, vj, 0.0)), H - 2)
+                fx, fy = uj - x0, vj - y0
+                xi, yi = x0.astype(np.intp), y0.astype(np.intp)
+                t00, t01, t10, t11 = ds[j][yi, xi], ds[j][yi, xi + 1], ds[j][yi + 1, xi], ds[j][yi + 1, xi + 1]
+                taps = ok[j][yi, xi] & ok[j][yi, xi + 1] & ok[j][yi + 1, xi] & ok[j][yi + 1, xi + 1]
+                top = t00 + fx * (t01 - t00)
+                bot = t10 + fx * (t11 - t10)
+                s = top + fy * (bot - top)
+                votes[i - c0] += inside & taps & (np.abs(z - s) <= tol * np.minimum(z, s))
+    return votes
+
+
+def mask_views_numpy(key, payload, votes, min_views):
+    """What td_cloud_views does to the pairs of keys_numpy: a pixel that is still valid and has fewer than ``min_views`` votes gets
+    INVALID_KEY and payload 0 -> (key, payload, votes with 0 where the key was invalid already, int64 [2]: tested, dropped)."""
+    key, payload = np.asarray(key, np.int64).reshape(-1), np.asarray(payload, np.uint64).reshape(-1)
+    flat = np.asarray(votes, np.uint8).reshape(-1)
+    tested = key != INVALID_KEY
+    drop = tested & (flat < int(min_views))
+    return (np.where(drop, INVALID_KEY, key).astype(np.int64), np.where(drop, np.uint64(0), payload).astype(np.uint64),
+            np.where(tested, flat, 0).astype(np.uint8).reshape(np.shape(votes)), np.array([tested.sum(), drop.sum()], np.int64))
+
+
 def voxel_table_numpy(key, rows):
     """Points (key int64 [n]; rows: uint64 payloads [n] or int64 rows [n,7]) -> (keys int64 [V] ascending, sums int64 [V,7]): sort,
     np.unique, np.add.reduceat.  Invalid keys are dropped."""
@@ -206,22 +312,34 @@ def finish_numpy(keys, sums, voxel, min_count=1):
     return xyz, rgb, count, n >= int(min_count)
 
 
-def _stats(counts, voxels, kept):
+def _stats(counts, voxels, kept, invalid_views=None):
     out = {"points": int(np.sum(counts))}
     out.update({name: int(v) for name, v in zip(CAUSES, counts)})
+    if invalid_views is not None:          # the multi-view filter is on: it took these from the valid pixels
+        out["valid"], out["invalid_views"] = out["valid"] - int(invalid_views), int(invalid_views)
     out["voxels"], out["voxels_dropped"] = int(voxels), int(voxels) - int(kept)
     return out
 
 
 def fuse_numpy(depth, color, poses, inv_K, voxel=DEFAULT_VOXEL, stride=1, border=0, min_depth=DEFAULT_MIN_DEPTH,
-               max_range=DEFAULT_MAX_RANGE, edge=0.0, min_count=1, depth_scale=1.0, pose_scale=1.0):
-    """All frames at once -> Cloud of numpy arrays: keys_numpy, voxel_table_numpy, finish_numpy."""
+               max_range=DEFAULT_MAX_RANGE, edge=0.0, min_count=1, depth_scale=1.0, pose_scale=1.0, min_views=0,
+               view_radius=DEFAULT_VIEW_RADIUS, view_tol=DEFAULT_VIEW_TOL, K=None, debug=None):
+    """All frames at once -> Cloud of numpy arrays: keys_numpy, with ``min_views`` > 0 views_numpy over all frames (every frame a
+    centre, every frame a possible neighbour) and mask_views_numpy, then voxel_table_numpy, finish_numpy.  ``K``: the 3x3 block the
+    filter projects with (default: the inverse of inv_K's);  ``debug``: a dict that receives the filter's "votes" [B,H,W]."""
     _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
+    _check_view_params(min_views, view_radius, view_tol)
     key, payload, counts = keys_numpy(depth, color, poses, inv_K, depth_scale, pose_scale, 1.0 / float(voxel), stride, border, min_depth,
                                       max_range, edge)
+    dropped = None
+    if min_views > 0:
+        votes = views_numpy(depth, poses, inv_K, _view_K9(K, inv_K), view_radius, view_tol, depth_scale, pose_scale, min_depth, max_range)
+        key, payload, votes, (_, dropped) = mask_views_numpy(key, payload, votes, min_views)
+        if debug is not None:
+            debug["votes"] = votes
     keys, sums = voxel_table_numpy(key, payload)
     xyz, rgb, count, keep = finish_numpy(keys, sums, voxel, min_count)
-    return Cloud(xyz[keep], rgb[keep], count[keep], keys[keep], _stats(counts, len(keys), int(keep.sum())))
+    return Cloud(xyz[keep], rgb[keep], count[keep], keys[keep], _stats(counts, len(keys), int(keep.sum()), dropped))
 
 
 def save_ply(path, xyz, rgb, count):
@@ -310,6 +428,40 @@ def keys_hip(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_vo
     return key, payload
 
 
+def views_hip(depth, poses, inv_K, K, radius, tol, depth_scale=1.0, pose_scale=1.0, min_depth=DEFAULT_MIN_DEPTH,
+              max_range=DEFAULT_MAX_RANGE, centres=None, bounds=None, key=None, payload=None, min_views=0, stats=None, votes=True):
+    """views_numpy as one launch of td_cloud_views -> votes uint8 [c1-c0,H,W] (None with ``votes`` false).  ``depth`` and ``poses``
+    are the whole window's.  ``key``, ``payload``: the int64 [(c1-c0) H W] pairs keys_hip wrote for the centre frames, changed in
+    place as mask_views_numpy changes them (a pixel whose key is invalid already is skipped: 0 votes); without them every pixel is
+    evaluated and only the votes are written.  ``stats``: an int64 [2] device tensor that the launch increments by the numbers of
+    pixels tested and dropped, or None."""
+    native.require_device(depth, poses)
+    if depth.dtype != torch.float32 or depth.dim() != 3 or poses.dtype != torch.float64 or tuple(poses.shape) != (depth.shape[0], 3, 4):
+        raise ValueError("depth float32 [N,H,W], poses float64 [N,3,4]; got %s %s, %s %s" % (
+            tuple(depth.shape), depth.dtype, tuple(poses.shape), poses.dtype))
+    N, H, W = depth.shape
+    radius, c0, c1, lo, hi = _view_ranges(N, H, W, radius, tol, centres, bounds)
+    if not 0 <= int(min_views) <= 2 * radius:
+        raise ValueError("min_views: 0 ... 2 radius = %d, got %r" % (2 * radius, min_views))
+    n = (c1 - c0) * H * W
+    if (key is None) != (payload is None) or (key is None and not votes):
+        raise ValueError("key and payload come together, and without them the votes are the only result")
+    if key is not None:
+        for t, name in ((key, "key"), (payload, "payload")):
+            if _i64(t, name, n) is not t:          # changed in place: a copy would take the result away
+                raise ValueError("%s: a contiguous tensor" % name)
+    if stats is not None:
+        stats = _i64(stats, "stats", 2)
+    m, k = _inv_K9(inv_K), _inv_K9(K, "K")
+    out = torch.empty(c1 - c0, H, W, dtype=torch.uint8, device=depth.device) if votes else None
+    if n == 0:                           # an empty tensor has no pointer to pass
+        return out
+    native.call("td_cloud_views", depth.contiguous(), poses.contiguous(), (ctypes.c_double * 9)(*k), (ctypes.c_double * 9)(*m), N, H, W,
+                c0, c1, lo, hi, radius, int(min_views), float(tol), float(depth_scale), float(pose_scale), float(min_depth),
+                float(max_range), key, payload, out, stats)
+    return out
+
+
 def heads_hip(sorted_keys):
     """Sorted int64 keys [N] -> int32 [N]: 1 where a valid key differs from its predecessor (td_cloud_heads)."""
     keys = _i64(sorted_keys, "sorted_keys")
@@ -390,39 +542,67 @@ def merge_hip(keys_a, sums_a, keys_b, sums_b):
 class _DeviceMap:
     """The running voxel map: sorted unique keys and their rows, plus the pixel counters."""
 
-    def __init__(self, device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale):
+    def __init__(self, device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale, min_views=0,
+                 view_radius=DEFAULT_VIEW_RADIUS, view_tol=DEFAULT_VIEW_TOL, K=None):
+        _check_view_params(min_views, view_radius, view_tol)
         self.args = (inv_K, float(depth_scale), float(pose_scale), 1.0 / float(voxel), stride, border, min_depth, max_range, edge)
         self.keys = torch.zeros(0, dtype=torch.int64, device=device)
         self.sums = torch.zeros(0, 7, dtype=torch.int64, device=device)
         self.counts = torch.zeros(6, dtype=torch.int64, device=device)
+        self.min_views, self.radius = int(min_views), int(view_radius)
+        if self.min_views:
+            self.view_args = (inv_K, _view_K9(K, inv_K), self.radius, float(view_tol), float(depth_scale), float(pose_scale), min_depth,
+                              max_range)
+            self.view_counts = torch.zeros(2, dtype=torch.int64, device=device)
 
-    def add(self, depth, color, poses):
+    def add(self, depth, color, poses, window=None, votes=False):
+        """One batch of centre frames.  With the filter on, ``window`` = (depth [n,H,W], poses [n,3,4], centres, bounds): the frames
+        the batch's neighbours come from and where the batch and the sequence's ends lie in them -> the votes, if asked for."""
         key, payload = keys_hip(depth, color, poses, *self.args, stats=self.counts)
+        out = None
+        if self.min_views:
+            out = views_hip(window[0], window[1], *self.view_args, centres=window[2], bounds=window[3], key=key, payload=payload,
+                            min_views=self.min_views, stats=self.view_counts, votes=votes)
         self.keys, self.sums = merge_hip(self.keys, self.sums, *table_hip(key, payload))
+        return out
 
     def cloud(self, voxel, min_count):
         xyz, rgb, count, keep = finish_hip(self.keys, self.sums, voxel, min_count)
         keep = keep.bool()
         out = (xyz[keep], rgb[keep], count[keep], self.keys[keep])
-        return Cloud(*out, _stats(self.counts.cpu().numpy(), self.keys.shape[0], out[3].shape[0]))
+        dropped = int(self.view_counts[1].item()) if self.min_views else None
+        return Cloud(*out, _stats(self.counts.cpu().numpy(), self.keys.shape[0], out[3].shape[0], dropped))
 
 
 def fuse_hip(depth, color, poses, inv_K, voxel=DEFAULT_VOXEL, batch_size=None, stride=1, border=0, min_depth=DEFAULT_MIN_DEPTH,
-             max_range=DEFAULT_MAX_RANGE, edge=0.0, min_count=1, depth_scale=1.0, pose_scale=1.0):
-    """fuse_numpy on the device, ``batch_size`` frames at a time (default: all at once) -> Cloud of device tensors."""
+             max_range=DEFAULT_MAX_RANGE, edge=0.0, min_count=1, depth_scale=1.0, pose_scale=1.0, min_views=0,
+             view_radius=DEFAULT_VIEW_RADIUS, view_tol=DEFAULT_VIEW_TOL, K=None, debug=None):
+    """fuse_numpy on the device, ``batch_size`` frames at a time (default: all at once) -> Cloud of device tensors.  With
+    ``min_views`` > 0, per batch of centre frames: keys_hip, views_hip on those keys with all frames as the window, then the
+    unchanged table and merge; with 0 no td_cloud_views is launched."""
     _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
     native.require_device(depth, color, poses)
     n = depth.shape[0]
     step = n if batch_size is None else int(batch_size)
     if step < 1 and n:
         raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
-    vmap = _DeviceMap(depth.device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale)
+    vmap = _DeviceMap(depth.device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale, min_views,
+                      view_radius, view_tol, K)
+    votes = []
     for at in range(0, n, max(step, 1)):
-        vmap.add(depth[at:at + step], color[at:at + step], poses[at:at + step])
+        window = (depth, poses, (at, min(at + step, n)), (0, n)) if vmap.min_views else None
+        votes.append(vmap.add(depth[at:at + step], color[at:at + step], poses[at:at + step], window, debug is not None))
+    if debug is not None and vmap.min_views:
+        debug["votes"] = torch.cat(votes)
     return vmap.cloud(voxel, min_count)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+
+def dataset_K(dataset):
+    """The float64 3x3 block of the dataset's inputs["K"] (pixels at the dataset's frame size)."""
+    return np.ascontiguousarray(np.asarray(dataset[0]["K"], dtype=np.float64)[:3, :3])
+
 
 def dataset_inv_K(dataset):
     """The float64 inverse of the 3x3 block of the dataset's inputs["K"] (pixels at the dataset's frame size)."""
@@ -441,20 +621,30 @@ class SceneFuser:
                 DepthPredictor (which wants HWC input: one permuted copy of the batch's frames), keys_hip, torch.sort, heads / cumsum
                 / reduce, merge_hip into the running map, which stays sorted by key.  Memory: one batch of points plus the map.
                 Two host synchronisations per batch (the voxel counts of the batch and of the merged map size their outputs).
+                With ``min_views`` > 0 a sliding window of depth maps is held as well: every frame still goes through the depth
+                network once, a frame is filtered and fused (keys_hip, views_hip on those keys, then the table and the merge as
+                before) as soon as the last frame of its clamped window has been predicted, and at most batch_size + 2 view_radius
+                depth maps are held from one batch to the next.  The cloud does not depend on ``batch_size``.
                 'cpu': the host statements.
     voxel, min_depth, max_range  in the MODEL's units (the stereo baseline is 0.015 of them, x 36 gives metres); the defaults of these
                 and of ``edge`` are UNTUNED starting values
     stride, border   use every stride-th pixel in x and y; drop ``border`` pixels at every image edge
     edge        flying-pixel filter: a pixel whose depth differs from a 4-neighbour's by more than edge x the smaller one is dropped
     min_count   drop voxels that fewer points fell into
+    min_views, view_radius, view_tol   multi-view filter (0: off, and nothing of it runs): a pixel is kept only if at least min_views
+                of its frame's 2 view_radius neighbouring frames (the window is shifted, not shortened, at the ends of the fused
+                range ``frames``) see a depth within view_tol x the smaller of the two where the pixel's point projects into them;
+                the defaults of view_radius and view_tol are UNTUNED.  Cloud.stats gains invalid_views; valid / (valid +
+                invalid_views) is the share of pixels on which the frames agree, a figure of a checkpoint that needs no ground truth
     depth_scale, pose_scale  multiply the depths / the pose translations (ground-truth poses in metres: depth_scale = the model's
                 unit in metres, ~36 for the reference's stereo-trained checkpoints)
     """
 
     def __init__(self, model, height, width, device, voxel=DEFAULT_VOXEL, batch_size=12, precision="fp32", stride=1, border=0,
                  min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=DEFAULT_EDGE, min_count=1, depth_scale=1.0,
-                 pose_scale=1.0, post_process=False):
+                 pose_scale=1.0, post_process=False, min_views=0, view_radius=DEFAULT_VIEW_RADIUS, view_tol=DEFAULT_VIEW_TOL):
         _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
+        _check_view_params(min_views, view_radius, view_tol)
         self.device = infer.check_precision(device, precision, batch_size)
         self.on_hip = self.device.type == "cuda"
         self.model = model
@@ -463,6 +653,37 @@ class SceneFuser:
         self.voxel, self.min_count = float(voxel), int(min_count)
         self.params = dict(stride=int(stride), border=int(border), min_depth=float(min_depth), max_range=float(max_range),
                            edge=float(edge), depth_scale=float(depth_scale), pose_scale=float(pose_scale))
+        self.min_views = int(min_views)
+        if self.min_views:                 # off: the parameters of the filter reach nothing
+            self.params.update(min_views=self.min_views, view_radius=int(view_radius), view_tol=float(view_tol))
+
+    def _predict(self, color):
+        return self.predictor.predict(color.permute(0, 2, 3, 1).contiguous()).depth.contiguous()
+
+    def _fuse_filtered(self, vmap, resident, all_poses, first, last, depths, want_votes):
+        """The device path with the multi-view filter on.  ``window`` holds the depth maps of the frames w0 ... have-1; a centre is
+        fused once the last frame of its clamped window is among them, and the window then drops what no later centre needs.  The
+        ends of the window stand in for the ends of the fused range: a centre that is ready has its whole clamped window inside."""
+        r, step = vmap.radius, self.batch_size
+        start = lambda i: min(max(i - r, first), last - 1 - 2 * r)          # the first frame of centre i's clamped window
+        window, w0, centre, votes = None, first, first, []
+        for at in range(first, last, step):
+            depth = self._predict(resident[at:min(at + step, last)])
+            if depths is not None:
+                depths.append(depth)
+            window = depth if window is None else torch.cat([window, depth])
+            have = at + depth.shape[0]
+            ready = centre
+            while ready < last and start(ready) + 2 * r < have:
+                ready += 1
+            while centre < ready:                                           # at most a batch of points at a time
+                c1 = min(centre + step, ready)
+                votes.append(vmap.add(window[centre - w0:c1 - w0], resident[centre:c1], all_poses[centre:c1],
+                                      (window, all_poses[w0:have], (centre - w0, c1 - w0), (0, have - w0)), want_votes))
+                centre = c1
+            if centre < last:
+                window, w0 = window[start(centre) - w0:], start(centre)
+        return torch.cat(votes) if want_votes else None
 
     def _poses(self, dataset, frames, poses):
         """float64 [n+1,3,4] camera-to-world, on the device (a numpy array on the host path)."""
@@ -479,31 +700,43 @@ class SceneFuser:
     def fuse(self, dataset, poses=None, frames=None, debug=None):
         """``poses``: any [n+1,3,4] camera-to-world array (KITTI ground truth with the user's depth_scale); None: the model's own.
         ``frames``: (first, last + 1) of the n+1 frames to fuse (poses are still computed from frame 0).  ``debug``: a dict that
-        receives the "depth" maps [m,H,W] and the "poses" [n+1,3,4] that were fused."""
+        receives the "depth" maps [m,H,W] and the "poses" [n+1,3,4] that were fused and, with the multi-view filter on, the "votes"
+        uint8 [m,H,W] of the pixels it tested (0 where a single-frame filter had dropped the pixel already)."""
         host_frames = odometry.dataset_frames_u8(dataset)
         m = host_frames.shape[0]
         first, last = (0, m) if frames is None else (int(frames[0]), int(frames[1]))
         if not 0 <= first < last <= m:
             raise ValueError("frames: 0 <= first < last <= %d, got %r" % (m, frames))
+        if self.min_views and last - first < 2 * self.params["view_radius"] + 1:
+            raise ValueError("view_radius %d needs %d frames to fuse, got %d" % (
+                self.params["view_radius"], 2 * self.params["view_radius"] + 1, last - first))
         inv_K = dataset_inv_K(dataset)
+        view_K = {"K": dataset_K(dataset)} if self.min_views else {}
         resident = host_frames.to(self.device)                                   # every frame: one upload, as bytes
         all_poses = self._poses(dataset, resident, poses)
-        depths = []
+        depths, votes = [], {}
         with torch.no_grad():
             if self.on_hip:
-                vmap = _DeviceMap(self.device, inv_K, self.voxel, **self.params)
-            for at in range(first, last, self.batch_size):
-                color = resident[at:min(at + self.batch_size, last)]
-                depth = self.predictor.predict(color.permute(0, 2, 3, 1).contiguous()).depth.contiguous()
-                if self.on_hip:
-                    vmap.add(depth, color, all_poses[at:at + color.shape[0]])
-                if debug is not None or not self.on_hip:
-                    depths.append(depth)
+                vmap = _DeviceMap(self.device, inv_K, self.voxel, **self.params, **view_K)
+            if self.on_hip and self.min_views:
+                votes["votes"] = self._fuse_filtered(vmap, resident, all_poses, first, last, None if debug is None else depths,
+                                                     debug is not None)
+            else:
+                for at in range(first, last, self.batch_size):
+                    color = resident[at:min(at + self.batch_size, last)]
+                    depth = self._predict(color)
+                    if self.on_hip:
+                        vmap.add(depth, color, all_poses[at:at + color.shape[0]])
+                    if debug is not None or not self.on_hip:
+                        depths.append(depth)
             if self.on_hip:
                 cloud = vmap.cloud(self.voxel, self.min_count)
             else:
                 cloud = fuse_numpy(torch.cat(depths).numpy(), host_frames[first:last].numpy(), all_poses[first:last], inv_K, self.voxel,
-                                   min_count=self.min_count, **self.params)
+                                   min_count=self.min_count, debug=votes, **self.params, **view_K)
+                if "votes" in votes:
+                    votes["votes"] = torch.from_numpy(votes["votes"])
         if debug is not None:
             debug["depth"], debug["poses"] = torch.cat(depths), all_poses
+            debug.update(votes)
         return cloud

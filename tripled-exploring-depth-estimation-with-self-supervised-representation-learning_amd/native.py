@@ -126,6 +126,8 @@ SIGNATURES = {
     "td_cloud_reduce_packed": (_I, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
     "td_cloud_reduce_rows": (_I, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
     "td_cloud_finish": (_I, [_P, _P, ctypes.c_longlong, ctypes.c_double, ctypes.c_longlong, _P, _P, _P, _P, _P]),
+    "td_cloud_views": (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
     "td_velo_depth_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
     "td_velo_depth": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P]),
 }
