@@ -842,6 +842,40 @@ long long td_velo_depth_workspace_bytes(int B, int Hmax, int Wmax);
 int td_velo_depth(const float* points, const long long* offsets, int B, const double* P, const int* sizes, int Hmax, int Wmax,
                   int vel_depth, void* workspace, long long workspace_bytes, float* gt, long long* stats, td_stream_t stream);
 
+/*
+ * A point cloud drawn into a batch of camera views: a z-buffered point renderer (csrc/td_render.hip, tripled_amd/render.py).  The
+ * reference has no such program: the statement is tripled_amd/render.py:render_numpy, which the kernels equal bit for bit.
+ *
+ * td_cloud_render: two fills and two launches whatever C is (one launch with V = 0), no synchronisation, no copy to the host, no
+ *   allocation.
+ *   xyz [V,3] float32, rgb [V,3] uint8: the cloud (device);  poses [C,3,4] float64, camera-to-world (device);  K: a HOST array, the nine
+ *        float64 entries of the 3x3 block, in pixels (the third row is not read);  bg_r, bg_g, bg_b: the background colour, 0 ... 255
+ *   per point i and camera c, float64, every product, sum and quotient rounded on its own ([R|t]: the pose):
+ *        e_k = (double)xyz_k - pose_scale t_k;  q_k = (R_0k e_0 + R_1k e_1) + R_2k e_2  (the transpose of R);  z = q_2
+ *        perspective:   u = ((K00 q_0 + K01 q_1) + K02 q_2) / z;  v = ((K10 q_0 + K11 q_1) + K12 q_2) / z;  s = (splat K00) / z
+ *        orthographic:  u = (K00 q_0 + K01 q_1) + K02;            v = (K10 q_0 + K11 q_1) + K12;            s = splat K00
+ *        in_range = z_near <= z <= z_far  (a NaN fails);  ui = rint(u), vi = rint(v)  (half to even; pixel centres at integer
+ *        coordinates);  r = min(8, floor(0.5 s))  (TD_RENDER_MAX_SPLAT = 8)
+ *        visible = in_range and ui + r >= 0 and ui - r <= W-1 and vi + r >= 0 and vi - r <= H-1  (in float64; a NaN fails)
+ *        every pixel of the square [ui-r, ui+r] x [vi-r, vi+r] inside the image takes the minimum of its entry and
+ *        (bits of (float)z) << 32 | i:  the nearest point, and among equal (float)z the lowest index
+ *   depth [C,H,W] float32 (out): (float)z of the pixel's point, 0 where nothing was drawn;  color [C,3,H,W] uint8 (out): its rgb, the
+ *        background where nothing was drawn;  index [C,H,W] int32 (out): i, -1 where nothing was drawn
+ *   stats [C,5] int64 (out): points, out of range, outside (in range, the square misses the image), drawn, pixels hit
+ *   workspace: td_cloud_render_workspace_bytes(C, H, W) bytes (0: unsupported shape), 8-byte aligned: one 64-bit integer per pixel
+ *   TD_ERR_BAD_ARG before any launch: a null pointer (also with V = 0), C <= 0, H < 1, W < 1, V < 0, z_near not > 0, z_far not finite
+ *        or below z_near, splat negative or not finite, a background outside 0 ... 255, a workspace that is too small or misaligned.
+ *        TD_ERR_UNSUPPORTED: C > 65535, H W > 2^31 - 1, V >= 2^31 - 1 (the index is the low word of a table entry).
+ *   V = 0 is legal: only the fills and the resolve run, and every pixel is background.
+ *   The table is a 64-bit integer minimum: no floating-point atomics, no kernel waits on another workgroup, two calls on the same
+ *   inputs return the same bits.
+ */
+long long td_cloud_render_workspace_bytes(int C, int H, int W);
+int td_cloud_render(const float* xyz, const uint8_t* rgb, long long V, const double* poses, const double* K, int C, int H, int W,
+                    double pose_scale, double z_near, double z_far, double splat, int ortho, int bg_r, int bg_g, int bg_b,
+                    void* workspace, long long workspace_bytes, float* depth, uint8_t* color, int* index, long long* stats,
+                    td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

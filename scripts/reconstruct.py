@@ -5,7 +5,7 @@ voxel-averaged coloured point cloud (binary PLY: x y z float, red green blue uch
   python scripts/reconstruct.py --config config/cfg_kitti_tripleD.py --checkpoint work/epoch_20.pth --data_path /data/kitti_odom \
          --sequence 9 [--frames A:B] [--poses FILE] [--voxel V] [--stride S] [--border P] [--max_range R] [--edge E] [--min_count N] \
          [--min_views M] [--view_radius R] [--view_tol T] [--depth_scale S] [--pose_scale S] [--batch_size 12] [--precision bf16] \
-         [--post_process] [--device cpu] --out cloud.ply
+         [--post_process] [--device cpu] [--save_poses FILE] --out cloud.ply
 
 Frames: <data_path>/sequences/NN/image_0/%06d.png; the frame count is the line count of <data_path>/poses/NN.txt (or of --poses).
 Without --poses the model's own poses are used (depth and pose share the model's scale); --poses FILE takes camera-to-world poses
@@ -15,7 +15,8 @@ keeps a pixel only if at least M of the 2 R frames around its own (--view_radius
 the pixel's point projects into them; the defaults of R and T are untuned as well.  With it the statistics gain invalid_views, and
 the last line is the consistency rate, the kept pixels over the tested ones: a figure of a checkpoint that needs no ground truth.
 The work is tripled_amd.cloud.SceneFuser (csrc/td_cloud.hip and csrc/td_views.hip on a HIP device); without --min_views the last
-line printed is the statistics.
+line printed is the statistics.  --save_poses FILE writes the camera-to-world poses that were fused (the model's own, or --poses')
+in KITTI pose text: what scripts/render_cloud.py needs to look at the cloud from where the frames were taken.
 """
 import argparse
 import os
@@ -59,6 +60,7 @@ def main():
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     ap.add_argument("--post_process", action="store_true")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--save_poses", default=None, help="write the poses that were fused, in KITTI pose text")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     cfg = Config.fromfile(args.config)
@@ -87,6 +89,10 @@ def main():
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     cloud.save_ply(args.out, result.xyz, result.rgb, result.count)
     print("saved %d points to %s" % (len(result.keys), args.out))
+    if args.save_poses:
+        os.makedirs(os.path.dirname(os.path.abspath(args.save_poses)), exist_ok=True)
+        odometry.save_kitti_poses(args.save_poses, fuser.poses)
+        print("saved %d poses to %s" % (len(fuser.poses), args.save_poses))
     print(" ".join("%s %d" % (k, v) for k, v in result.stats.items()))
     if args.min_views:
         kept, tested = result.stats["valid"], result.stats["valid"] + result.stats["invalid_views"]

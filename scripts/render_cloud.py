@@ -1,0 +1,127 @@
+#!/usr/bin/env python3
+"""Look at a fused point cloud: the PLY of scripts/reconstruct.py drawn into the cameras of a pose file, and from above.  No model
+and no checkpoint are needed.  The reference has no such program.
+
+  python scripts/render_cloud.py --cloud cloud.ply --poses poses.txt [--frames A:B] [--every N] \
+         (--config config/cfg_kitti_tripleD.py | --K fx fy cx cy) [--height H --width W] [--near Z] [--far Z] [--splat S] \
+         [--pose_scale S] [--top] [--save_depth] [--device cpu] --out DIR
+
+--poses: camera-to-world poses in KITTI pose text (reconstruct.py --save_poses writes the ones a cloud was fused with; with the
+ground truth give the --pose_scale the cloud was fused with).  --frames A:B takes the poses A ... B-1, --every N every N-th of them.
+The camera is the config's (the KITTI intrinsics of the datasets at the config's height x width, or at --height x --width) or
+--K fx fy cx cy in pixels with --height and --width.  --near, --far and --splat (the world size a point is drawn with; 0: one pixel
+per point) are in the cloud's units, and their defaults are untuned starting values.  A point is drawn as a square in the image, not
+as a disc in space, and points seen through the gaps between squares are drawn.
+Writes view_%06d_color.png and view_%06d_depth.png per pose (the number is the pose's line; the depth in magma between the smallest
+and the largest depth drawn, black where nothing was drawn), with --save_depth view_%06d_depth.npy (float32, 0 where nothing was
+drawn), and with --top top_color.png / top_depth.png: the cloud from above, orthographic, the sequence's forward direction up.  Prints
+the statistics per view and, last, the mean share of pixels hit.  The work is tripled_amd.render.CloudRenderer (csrc/td_render.hip on
+a HIP device).
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+from PIL import Image
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import tripled_amd  # noqa: F401,E402
+from tripled_amd import cloud, infer, odometry, render  # noqa: E402
+
+
+def depth_picture(depth):
+    """float32 [H,W] -> uint8 [H,W,3]: magma between the smallest and the largest depth drawn, black where nothing was drawn."""
+    hit = depth > 0
+    if not hit.any():
+        return np.zeros(depth.shape + (3,), np.uint8)
+    picture = infer.colorize_numpy(depth, depth[hit].min(), depth[hit].max())
+    picture[~hit] = 0
+    return picture
+
+
+def save_view(out_dir, stem, depth, color, save_depth=False):
+    Image.fromarray(np.ascontiguousarray(color.transpose(1, 2, 0))).save(os.path.join(out_dir, stem + "_color.png"))
+    Image.fromarray(depth_picture(depth)).save(os.path.join(out_dir, stem + "_depth.png"))
+    if save_depth:
+        np.save(os.path.join(out_dir, stem + "_depth.npy"), depth)
+
+
+def stats_line(name, stats, pixels):
+    return "%s %s share_hit %.4f" % (name, " ".join("%s %d" % (k, v) for k, v in zip(render.STATS, stats)), stats[4] / pixels)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cloud", required=True, help="the PLY of scripts/reconstruct.py")
+    ap.add_argument("--poses", required=True, help="camera-to-world poses in KITTI pose text")
+    ap.add_argument("--frames", default=None, help="A:B, the poses A ... B-1 (default: all)")
+    ap.add_argument("--every", type=int, default=1)
+    ap.add_argument("--config", default=None)
+    ap.add_argument("--K", type=float, nargs=4, default=None, metavar=("FX", "FY", "CX", "CY"), help="pixels at --height x --width")
+    ap.add_argument("--height", type=int, default=None, help="default: the config's")
+    ap.add_argument("--width", type=int, default=None)
+    ap.add_argument("--near", type=float, default=render.DEFAULT_NEAR)
+    ap.add_argument("--far", type=float, default=render.DEFAULT_FAR)
+    ap.add_argument("--splat", type=float, default=render.DEFAULT_SPLAT)
+    ap.add_argument("--pose_scale", type=float, default=1.0)
+    ap.add_argument("--top", action="store_true", help="also the cloud from above")
+    ap.add_argument("--save_depth", action="store_true")
+    ap.add_argument("--batch_size", type=int, default=12)
+    ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--out", required=True)
+    args = ap.parse_args()
+    if (args.config is None) == (args.K is None):
+        ap.error("one of --config and --K")
+    if args.every < 1:
+        ap.error("--every: at least 1")
+    if args.config:
+        from mmcv import Config
+        from mono.datasets.kitti_dataset import KITTIDataset
+        cfg = Config.fromfile(args.config)
+        height, width = args.height or cfg.model["height"], args.width or cfg.model["width"]
+        K = KITTIDataset.K.copy()                # normalised; the datasets scale it like this (float32)
+        K[0, :] *= width
+        K[1, :] *= height
+        K = K[:3, :3].astype(np.float64)
+    else:
+        if not (args.height and args.width):
+            ap.error("--K needs --height and --width")
+        height, width = args.height, args.width
+        fx, fy, cx, cy = args.K
+        K = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
+    points = cloud.load_ply(args.cloud)
+    xyz = np.stack([points["x"], points["y"], points["z"]], 1).astype(np.float32)
+    rgb = np.stack([points["red"], points["green"], points["blue"]], 1).astype(np.uint8)
+    poses = odometry.load_kitti_poses(args.poses)
+    a, _, b = (args.frames or ":").partition(":")
+    numbers = list(range(int(a or 0), min(int(b or len(poses)), len(poses)), args.every))
+    if not numbers:
+        ap.error("--frames %s of %d poses: nothing to draw" % (args.frames, len(poses)))
+    os.makedirs(args.out, exist_ok=True)
+    renderer = render.CloudRenderer(args.device, height, width, K, near=args.near, far=args.far, splat=args.splat,
+                                    pose_scale=args.pose_scale, batch_size=args.batch_size)
+    print("-> Drawing %d points into %d views of %d x %d" % (len(xyz), len(numbers), height, width))
+    shares = []
+    resident = renderer.upload(xyz, rgb)                          # once; a batch of views at a time is held on the host
+    for at in range(0, len(numbers), args.batch_size):
+        batch = numbers[at:at + args.batch_size]
+        out = renderer.render(*resident, poses[batch])
+        for j, n in enumerate(batch):
+            save_view(args.out, "view_%06d" % n, out.depth[j], out.color[j], args.save_depth)
+            print(stats_line("view %06d" % n, out.stats[j], height * width))
+            shares.append(out.stats[j, 4] / (height * width))
+    if args.top:
+        pose, top_K = render.top_view(xyz, height, width, near=args.near)
+        finite = xyz[np.isfinite(xyz).all(1)]
+        far = 3.0 * args.near + float(finite[:, 1].max() - finite[:, 1].min())        # the lowest point is at 2 near + the box's height
+        out = renderer.render(*resident, pose[None], K=top_K, ortho=True, far=far, pose_scale=1.0)
+        save_view(args.out, "top", out.depth[0], out.color[0])
+        print(stats_line("top", out.stats[0], height * width))
+    print("mean share of pixels hit %.4f over %d views" % (float(np.mean(shares)), len(shares)))
+
+
+if __name__ == "__main__":
+    main()

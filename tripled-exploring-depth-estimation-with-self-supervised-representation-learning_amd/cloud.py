@@ -654,6 +654,7 @@ class SceneFuser:
         self.params = dict(stride=int(stride), border=int(border), min_depth=float(min_depth), max_range=float(max_range),
                            edge=float(edge), depth_scale=float(depth_scale), pose_scale=float(pose_scale))
         self.min_views = int(min_views)
+        self.poses = None                  # float64 [n+1,3,4] on the host: the poses of the last fuse()
         if self.min_views:                 # off: the parameters of the filter reach nothing
             self.params.update(min_views=self.min_views, view_radius=int(view_radius), view_tol=float(view_tol))
 
@@ -701,7 +702,8 @@ class SceneFuser:
         """``poses``: any [n+1,3,4] camera-to-world array (KITTI ground truth with the user's depth_scale); None: the model's own.
         ``frames``: (first, last + 1) of the n+1 frames to fuse (poses are still computed from frame 0).  ``debug``: a dict that
         receives the "depth" maps [m,H,W] and the "poses" [n+1,3,4] that were fused and, with the multi-view filter on, the "votes"
-        uint8 [m,H,W] of the pixels it tested (0 where a single-frame filter had dropped the pixel already)."""
+        uint8 [m,H,W] of the pixels it tested (0 where a single-frame filter had dropped the pixel already).  The poses that were
+        used stay in ``self.poses`` (float64 [n+1,3,4] on the host): what render.CloudRenderer needs to look at the cloud."""
         host_frames = odometry.dataset_frames_u8(dataset)
         m = host_frames.shape[0]
         first, last = (0, m) if frames is None else (int(frames[0]), int(frames[1]))
@@ -714,6 +716,7 @@ class SceneFuser:
         view_K = {"K": dataset_K(dataset)} if self.min_views else {}
         resident = host_frames.to(self.device)                                   # every frame: one upload, as bytes
         all_poses = self._poses(dataset, resident, poses)
+        self.poses = all_poses.cpu().numpy() if torch.is_tensor(all_poses) else np.array(all_poses)
         depths, votes = [], {}
         with torch.no_grad():
             if self.on_hip:

@@ -130,6 +130,9 @@ SIGNATURES = {
                             ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
     "td_velo_depth_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
     "td_velo_depth": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P]),
+    "td_cloud_render_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
+    "td_cloud_render": (_I, [_P, _P, ctypes.c_longlong, _P, ctypes.POINTER(ctypes.c_double), _I, _I, _I, ctypes.c_double, ctypes.c_double,
+                             ctypes.c_double, ctypes.c_double, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
