@@ -876,6 +876,59 @@ int td_cloud_render(const float* xyz, const uint8_t* rgb, long long V, const dou
                     void* workspace, long long workspace_bytes, float* depth, uint8_t* color, int* index, long long* stats,
                     td_stream_t stream);
 
+/*
+ * A fused cloud scored against the lidar scans (csrc/td_scan.hip, csrc/td_nn.hip, tripled_amd/cloud_eval.py).  The reference has
+ * no such program: the statements are cloud_eval.scan_keys_numpy and cloud_eval.nearest_numpy (itself pinned by an all-pairs brute
+ * force), which the kernels equal bit for bit.
+ *
+ * td_scan_keys: one launch, S velodyne scans of mixed lengths -> the (key, payload) pairs of td_cloud_keys, which the unchanged
+ *   sort / td_cloud_heads / td_cloud_reduce_* / td_cloud_finish chain fuses.
+ *   points [n,4] float32 (x, y, z, reflectance), the scans concatenated (a 16-byte aligned base is read 16 bytes at a time);
+ *   offsets [S+1] int64 (device): scan s owns points offsets[s] .. offsets[s+1]-1, found per point by a bounded binary search;
+ *   Tr: a HOST array, 3x4 float64 velodyne-to-camera (the Tr: line of the odometry calib.txt);  poses [S,3,4] float64 camera-to-world
+ *   (device);  K: a HOST array, the nine float64 entries of the 3x3 block in pixels (rows 0 and 1 are read), NULL allowed with H = 0;
+ *   H, W: the image the view test keeps points in, H = 0: no view test.
+ *   float64, every product, sum and quotient rounded on its own:
+ *     cam_k   = ((Tr_k0 x + Tr_k1 y) + Tr_k2 z) + Tr_k3
+ *     u = ((K00 cam_x + K01 cam_y) + K02 cam_z) / cam_z;  v likewise from row 1
+ *     world_k = ((r_k0 cam_x + r_k1 cam_y) + r_k2 cam_z) + t_k
+ *     key, q  = td_cloud_keys' formula from world inv_voxel
+ *     r = g = b = clamp(floor((double)reflectance 255.0 + 0.5), 0, 255), 0 for a NaN reflectance
+ *   a point is invalid (key INT64_MAX, payload 0) by the first cause that holds: point (x, y or z not finite, or no scan owns the
+ *     point), depth (cam_z outside [min_depth, max_range]; a NaN fails), view (H > 0 and not 0 <= u <= W-1 and 0 <= v <= H-1), range (a
+ *     voxel coordinate outside [-2^20, 2^20), or the key is the sentinel)
+ *   key [n] int64, payload [n] uint64 (out);  stats [5] int64 (device) or NULL: incremented by valid, point, depth, view, range (LDS
+ *     counters per workgroup, then at most five integer atomics per workgroup)
+ *   TD_ERR_BAD_ARG before any launch: a null points, offsets, Tr, poses, key or payload, K null with H > 0, n < 0, S < 1, H < 0, W < 0,
+ *     W < 1 with H > 0, inv_voxel not > 0, not min_depth <= max_range.  n = 0 is a successful no-op without a launch.
+ *
+ * td_nn_query: one launch, one thread per query: the nearest reference point within tau, exactly.
+ *   query [N,3] float64;  the reference as a sorted grid (cloud_eval.grid_hip): points [M,3] float64 in cell order, order [M] int64 (the
+ *   original index of every sorted point), cell_key [C] int64 ascending (td_cloud_keys' packing of floor(x inv_cell) per axis),
+ *   cell_start [C+1] int64;  inv_cell = (1 - 2^-20) / tau and tau2 = tau tau are computed on the host, in float64, by this function
+ *   and by the grid's builder alike.  |x - y| <= tau puts x and y in cells at most one apart on every axis, so the 27 cells around
+ *   the query's cell hold every candidate.
+ *   per candidate j: e = point_j - query;  d2 = ((e_x e_x) + (e_y e_y)) + (e_z e_z);  candidate iff d2 <= tau2;  the winner is the
+ *   smallest d2, among equal d2 the lowest order[j].  A neighbour cell outside [-2^20, 2^20) is skipped.  A query that is not finite
+ *   or whose cell is outside [-2^20, 2^20) is invalid.
+ *   d2 [N] float64 (out): +inf when nothing lies within tau or the query is invalid;  index [N] int64 (out): the winner's original
+ *   index, -1 likewise
+ *   thr2: a HOST array of K <= 16 squared thresholds (NULL allowed with K = 0);  counts [K+2] int64 (device), incremented:
+ *   counts[k] by the queries with d2 <= thr2[k], counts[K] by the queries that found a neighbour, counts[K+1] by the invalid queries
+ *   (LDS counters per workgroup, then at most K+2 64-bit integer atomics per workgroup)
+ *   Every index read from cell_start is clamped to [0, M] and every search stays inside [0, C): a malformed grid reads nothing
+ *   outside the buffers.  A thread's work is bounded by 27 x the largest cell population.
+ *   TD_ERR_BAD_ARG before any launch: a null query, cell_start, d2, index or counts, points or order null with M > 0, cell_key null
+ *     with C > 0, thr2 null with K > 0, N < 0, M < 0, C < 0, C > M, K outside 0 .. 16, tau not > 0 or not finite.  N = 0 is a
+ *     successful no-op without a launch;  M = 0 fills the "not found" answer.
+ */
+int td_scan_keys(const float* points, long long n, const long long* offsets, int S, const double* Tr, const double* poses,
+                 const double* K, int H, int W, double min_depth, double max_range, double inv_voxel, long long* key,
+                 unsigned long long* payload, long long* stats, td_stream_t stream);
+int td_nn_query(const double* query, long long N, const double* points, const long long* order, long long M, const long long* cell_key,
+                const long long* cell_start, long long C, double tau, const double* thr2, int K, double* d2, long long* index,
+                long long* counts, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,6 +133,10 @@ SIGNATURES = {
     "td_cloud_render_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
     "td_cloud_render": (_I, [_P, _P, ctypes.c_longlong, _P, ctypes.POINTER(ctypes.c_double), _I, _I, _I, ctypes.c_double, ctypes.c_double,
                              ctypes.c_double, ctypes.c_double, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P, _P, _P]),
+    "td_scan_keys": (_I, [_P, ctypes.c_longlong, _P, _I, ctypes.POINTER(ctypes.c_double), _P, ctypes.POINTER(ctypes.c_double), _I, _I,
+                          ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
+    "td_nn_query": (_I, [_P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, ctypes.c_double,
+                         ctypes.POINTER(ctypes.c_double), _I, _P, _P, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
