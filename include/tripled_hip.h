@@ -929,6 +929,47 @@ int td_nn_query(const double* query, long long N, const double* points, const lo
                 const long long* cell_start, long long C, double tau, const double* thr2, int K, double* d2, long long* index,
                 long long* counts, td_stream_t stream);
 
+/*
+ * A fused cloud aligned to the lidar by iterated closest points (csrc/td_align.hip, tripled_amd/cloud_align.py): x' = c R x + t maps
+ * the predicted cloud into the reference's frame.  The correspondences are td_nn_query's; the closed-form solve (Umeyama 1991, the
+ * reference's mono/tools/geometry.py umeyama_alignment) runs on the host on the 17 sums and the count below.  The statements are
+ * cloud_align.transform_numpy and cloud_align.moments_numpy, which the kernels equal bit for bit.  float64, every product and sum
+ * rounded on its own; no floating-point atomics, no kernel waits on another workgroup.
+ *
+ * td_cloud_transform: one launch, one thread per point.
+ *   src [N,3] float64;  c, and the HOST arrays R (nine float64, row-major) and t (three float64), are copied into the launch;
+ *   out [N,3] float64 (out), src itself allowed:
+ *     out_k = c ((R_k0 x + R_k1 y) + R_k2 z) + t_k
+ *   A row that is not finite gives a row that is not finite (which td_nn_query counts as invalid).
+ *   TD_ERR_BAD_ARG before any launch: a null src, R, t or out, N < 0, c or an entry of R or t not finite.  N = 0 is a successful
+ *     no-op without a launch.
+ *
+ * td_icp_moments: two launches (ceil(N / 256) workgroups, then one).
+ *   cur [N,3] float64: the transformed predicted points that were queried;  ref [M,3] float64: the reference in its ORIGINAL order,
+ *   the order td_nn_query's index refers to (NULL allowed with M = 0);  index [N] int64 and d2 [N] float64: td_nn_query's outputs;
+ *   origin: a HOST array of three float64, subtracted from both clouds before anything is multiplied.
+ *   Row i is matched iff 0 <= index_i < M and d2_i <= trim2 (a NaN fails).  With p = cur_i - origin and q = ref[index_i] - origin a
+ *   matched row contributes, in this order, the 17 values
+ *     p_x p_y p_z,  q_x q_y q_z,  q_r p_c (nine, row-major: r the slow index),  (p_x p_x + p_y p_y) + p_z p_z,  d2_i
+ *   and any other row +0.0 in every slot.  An index_i >= M or < -1 reads nothing and is counted as bad_index.
+ *   The order of the sums is fixed and depends on N alone.  Stage 1: workgroup b owns rows 256 b ... 256 b + 255 (rows past N are
+ *   +0.0) and reduces them by the halving tree: for s = 128, 64, ..., 1: row j += row j + s for every j < s; row 0 is
+ *   partials[b][17].  Stage 2: one workgroup; thread j adds partials[j], partials[j + 256], ... one after the other, in that order,
+ *   onto +0.0; the same tree over the 256 threads follows.
+ *   workspace: td_icp_moments_workspace(N) bytes (17 float64 per workgroup of stage 1; 0 for N = 0), 8-byte aligned
+ *     (TD_ERR_WORKSPACE if workspace_bytes is less)
+ *   out: 19 x 8 bytes (out): the 17 sums as float64, then matched and bad_index as int64.  All 19 are cleared first, also for
+ *     N = 0, which launches nothing else; the counters are added up in LDS per workgroup, then at most two 64-bit integer atomics per
+ *     workgroup.
+ *   TD_ERR_BAD_ARG before any launch: a null origin or out, N < 0, M < 0, trim2 not >= 0 (+inf is allowed: no trimming), an origin
+ *     that is not finite, workspace_bytes < 0, a workspace or out that is not 8-byte aligned; with N > 0: a null cur, index, d2 or
+ *     workspace, ref null with M > 0.
+ */
+int td_cloud_transform(const double* src, long long N, double c, const double* R, const double* t, double* out, td_stream_t stream);
+long long td_icp_moments_workspace(long long N);
+int td_icp_moments(const double* cur, long long N, const double* ref, long long M, const long long* index, const double* d2, double trim2,
+                   const double* origin, void* workspace, long long workspace_bytes, double* out, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

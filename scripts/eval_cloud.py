@@ -5,7 +5,9 @@ reference has no such program.
 
   python scripts/eval_cloud.py --cloud cloud.ply (--data_path ROOT --sequence 9 --poses FILE [--frames A:B] | --ref ref.ply) \
          [--config CFG | --K fx fy cx cy] [--height H --width W] [--ref_voxel V] [--min_depth Z] [--max_range R] [--tau T] \
-         [--thresholds T1 T2 ...] [--pred_scale S] [--batch_size 12] [--save_ref ref.ply] [--save_error error.ply] [--device cpu]
+         [--thresholds T1 T2 ...] [--pred_scale S] [--batch_size 12] [--save_ref ref.ply] [--save_error error.ply] [--device cpu] \
+         [--align {none,rigid,similarity} [--align_tau T] [--align_iters 30] [--align_trim D] [--align_stride 1] [--init_poses FILE] \
+          [--save_transform T.txt] [--save_aligned aligned.ply]]
 
 Scans: <data_path>/sequences/NN/velodyne/%06d.bin (float32 x y z reflectance), velodyne to camera from the "Tr:" line of
 <data_path>/sequences/NN/calib.txt.  --poses: camera-to-world poses in KITTI pose text, one per scan of the sequence, typically the
@@ -13,8 +15,16 @@ ground truth the cloud was fused with (reconstruct.py --poses gt.txt --depth_sca
 camera (--config: the datasets' KITTI intrinsics at the config's size or at --height x --width; or --K with --height and --width) only
 lidar points inside the camera's image are fused: without it the lidar's 360 degrees count against the recall of a forward-looking
 camera.  --ref takes a reference cloud that was saved earlier (--save_ref) instead of the scans.  --ref_voxel, --min_depth, --max_range
-and --tau are in the poses' units (metres for the ground truth); --pred_scale multiplies the predicted cloud and is the only alignment
-there is.  The defaults of --tau (three voxels of cloud.py's default) and --thresholds (tau/4, tau/2, tau) are UNTUNED.
+and --tau are in the poses' units (metres for the ground truth); --pred_scale multiplies the predicted cloud and, without --align, is
+the only alignment there is.  The defaults of --tau (three voxels of cloud.py's default) and --thresholds (tau/4, tau/2, tau) are UNTUNED.
+--align rigid | similarity first registers the predicted cloud to the reference by iterated closest points (tripled_amd.cloud_align:
+x' = c R x + t, point to point, predicted into reference) and scores the ALIGNED cloud.  The initial guess is --pred_scale, or, with
+--init_poses (the poses the cloud was fused with, reconstruct.py --save_poses; one per pose of --poses), the closed-form similarity
+between the two trajectories' camera centres: ICP cannot start from the identity when the scale is off by 36.  --align_tau is the
+radius of the correspondence search (default 2 tau), --align_trim leaves out correspondences farther apart (default: none),
+--align_stride uses every n-th point, --align_iters bounds the passes; all UNTUNED.  Prints the initial guess, one line per pass
+(matched, rms), the final scale, R, t and whether it converged; the score lines are then prefixed "aligned".  --save_transform writes
+the 4x4 [[c R, t], [0, 1]] as text, --save_aligned the aligned cloud with its colours.
 Prints the scan statistics, one line per cause; both clouds' sizes, dropped points and largest cell; one line per threshold with
 precision, recall and F-score; accuracy and completeness (the mean distance to the nearest neighbour, capped at tau).
 --save_error writes the predicted cloud coloured by min(distance, tau) / tau through the magma table, pure green (0, 255, 0) where
@@ -31,7 +41,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tripled_amd  # noqa: F401,E402
-from tripled_amd import cloud, cloud_eval, odometry, velodyne  # noqa: E402
+from tripled_amd import cloud, cloud_align, cloud_eval, odometry, velodyne  # noqa: E402
 
 
 def _host(t):
@@ -41,6 +51,39 @@ def _host(t):
 def _load_xyz(path):
     points = cloud.load_ply(path)
     return np.stack([points["x"], points["y"], points["z"]], 1).astype(np.float32), points
+
+
+def _align(args, pred_xyz, ref_xyz):
+    """--align: the initial guess, the passes and the result are printed; -> the aligned cloud, float64 [n,3] on the host."""
+    with_scale = args.align == "similarity"
+    init = (args.pred_scale, np.eye(3), np.zeros(3))
+    if args.init_poses:
+        gt, own = odometry.load_kitti_poses(args.poses), odometry.load_kitti_poses(args.init_poses)
+        if len(own) != len(gt):
+            raise SystemExit("--init_poses: %d poses, --poses has %d" % (len(own), len(gt)))
+        a, _, b = (args.frames or ":").partition(":")
+        rows = slice(int(a or 0), int(b or len(gt)))
+        if not with_scale:
+            own[:, :, 3] *= args.pred_scale              # rigid: the scale stays --pred_scale, so the centres are aligned at it
+        c, R, t = cloud_align.similarity_from_poses(own[rows], gt[rows], with_scale)
+        init = (c if with_scale else args.pred_scale, R, t)
+    align_tau = 2.0 * args.tau if args.align_tau is None else args.align_tau
+    print("-> Aligning (%s, tau %.6g, at most %d passes, stride %d)" % (args.align, align_tau, args.align_iters, args.align_stride))
+    print("initial scale %.9g R %s t %s" % (init[0], " ".join("%.9g" % v for v in np.reshape(init[1], -1)), " ".join("%.9g" % v for v in init[2])))
+    aligner = cloud_align.CloudAligner(args.device, align_tau, args.align, args.align_iters, args.align_trim, args.align_stride)
+    result = aligner.align(pred_xyz, ref_xyz, init)
+    for n, (matched, rms) in enumerate(result.history):
+        print("pass %d: matched %d rms %.6g" % (n, matched, rms))
+    print("scale %.9g R %s t %s" % (result.scale, " ".join("%.9g" % v for v in result.R.reshape(-1)), " ".join("%.9g" % v for v in result.t)))
+    print("converged %s after %d passes" % (result.converged, result.iterations))
+    if args.save_transform:
+        os.makedirs(os.path.dirname(os.path.abspath(args.save_transform)), exist_ok=True)
+        np.savetxt(args.save_transform, cloud_align.matrix(result.scale, result.R, result.t), fmt="%.17g")
+        print("saved the transform to %s" % args.save_transform)
+    if aligner.on_hip:
+        moved = cloud_align.transform_hip(torch.as_tensor(pred_xyz).to(aligner.device, torch.float64).contiguous(), result.scale, result.R, result.t)
+        return moved.cpu().numpy()
+    return cloud_align.transform_numpy(pred_xyz, result.scale, result.R, result.t)
 
 
 def main():
@@ -65,7 +108,19 @@ def main():
     ap.add_argument("--save_ref", default=None)
     ap.add_argument("--save_error", default=None)
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--align", choices=("none", "rigid", "similarity"), default="none", help="register the cloud to the reference first")
+    ap.add_argument("--align_tau", type=float, default=None, help="radius of the correspondence search (default: 2 tau, untuned)")
+    ap.add_argument("--align_iters", type=int, default=30)
+    ap.add_argument("--align_trim", type=float, default=None, help="leave out correspondences farther apart (default: align_tau)")
+    ap.add_argument("--align_stride", type=int, default=1, help="align on every n-th predicted point")
+    ap.add_argument("--init_poses", default=None, help="the poses the cloud was fused with; aligned to --poses for the initial guess")
+    ap.add_argument("--save_transform", default=None, help="the 4x4 [[c R, t], [0, 1]] as text")
+    ap.add_argument("--save_aligned", default=None, help="the aligned cloud (PLY)")
     args = ap.parse_args()
+    if args.align == "none" and (args.init_poses or args.save_transform or args.save_aligned):
+        ap.error("--init_poses, --save_transform and --save_aligned need --align rigid or similarity")
+    if args.init_poses and not args.poses:
+        ap.error("--init_poses needs --poses, the trajectory it is aligned to")
     if (args.ref is None) == (args.data_path is None):
         ap.error("one of --data_path (with --poses) and --ref")
     if args.data_path and not args.poses:
@@ -112,13 +167,21 @@ def main():
             os.makedirs(os.path.dirname(os.path.abspath(args.save_ref)), exist_ok=True)
             cloud.save_ply(args.save_ref, ref.xyz, ref.rgb, ref.count)
             print("saved %d reference points to %s" % (len(ref.keys), args.save_ref))
-    result = cloud_eval.CloudComparer(args.device, args.tau, args.thresholds).compare(pred_xyz, ref_xyz, args.pred_scale)
+    label, pred_scale = "", args.pred_scale
+    if args.align != "none":
+        pred_xyz = _align(args, pred_xyz, ref_xyz)
+        label, pred_scale = "aligned ", 1.0
+        if args.save_aligned:
+            os.makedirs(os.path.dirname(os.path.abspath(args.save_aligned)), exist_ok=True)
+            cloud.save_ply(args.save_aligned, pred_xyz, np.stack([pred["red"], pred["green"], pred["blue"]], 1), pred["count"])
+            print("saved %d aligned points to %s" % (len(pred_xyz), args.save_aligned))
+    result = cloud_eval.CloudComparer(args.device, args.tau, args.thresholds).compare(pred_xyz, ref_xyz, pred_scale)
     for name, n, grid in (("predicted", "n_pred", "pred_grid"), ("reference", "n_ref", "ref_grid")):
-        print("%s cloud: %d points, dropped %d, cells %d, max_cell %d" % (
-            name, result.stats[n], result.stats[grid]["dropped"], result.stats[grid]["cells"], result.stats[grid]["max_cell"]))
+        print("%s%s cloud: %d points, dropped %d, cells %d, max_cell %d" % (
+            label if name == "predicted" else "", name, result.stats[n], result.stats[grid]["dropped"], result.stats[grid]["cells"], result.stats[grid]["max_cell"]))
     for t, p, r, f in zip(result.thresholds, result.precision, result.recall, result.fscore):
-        print("threshold %.6g: precision %.4f recall %.4f fscore %.4f" % (t, p, r, f))
-    print("accuracy %.6g completeness %.6g (tau %.6g)" % (result.accuracy, result.completeness, args.tau))
+        print("%sthreshold %.6g: precision %.4f recall %.4f fscore %.4f" % (label, t, p, r, f))
+    print("%saccuracy %.6g completeness %.6g (tau %.6g)" % (label, result.accuracy, result.completeness, args.tau))
     if args.save_error:
         os.makedirs(os.path.dirname(os.path.abspath(args.save_error)), exist_ok=True)
         colors = cloud_eval.error_colors(_host(result.pred.d2), _host(result.pred.index), args.tau)

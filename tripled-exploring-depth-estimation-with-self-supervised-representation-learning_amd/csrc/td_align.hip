@@ -1,0 +1,165 @@
+// A fused cloud aligned to the lidar by iterated closest points (tripled_amd/cloud_align.py): the two device pieces of a loop whose
+// correspondences come from td_nn_query (td_nn.hip) and whose closed-form solve (Umeyama) runs on the host.
+//   td_cloud_transform   one thread per point: out = c R x + t
+//   td_icp_moments       the correspondences reduced to the 17 sums the closed form needs, plus two counters
+// float64 throughout, built with -ffp-contract=off: every product and sum is rounded on its own, in the order written here.  No
+// floating-point atomics and no kernel waits on another workgroup: the moments are summed in a FIXED order that depends on N alone
+// (stage 1: one workgroup per 256 consecutive rows, the LDS halving tree of td_odom.hip's block_reduce; stage 2: one workgroup, thread j
+// adds partials j, j + 256, ... in that order from +0.0, then the same tree), so the result is bit-reproducible and equals
+// cloud_align.moments_numpy bit for bit.  The counters are integers: LDS first, then one 64-bit atomic per workgroup and counter.
+#include <math.h>
+
+#include "td_common.h"
+
+namespace td {
+
+#define TD_ICP_SLOTS 17      // p (3), q (3), q_r p_c (9, row-major), |p|^2, d2
+
+struct TransformArgs {
+  const double* src;      // [N,3]
+  double* out;            // [N,3] (may be src)
+  long long N;
+  double c, R[9], t[3];
+};
+
+__global__ __launch_bounds__(TD_THREADS) void cloud_transform_kernel(const TransformArgs a) {
+  const long long i = (long long)blockIdx.x * TD_THREADS + threadIdx.x;
+  if (i >= a.N) return;
+  const double x = a.src[i * 3], y = a.src[i * 3 + 1], z = a.src[i * 3 + 2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) a.out[i * 3 + k] = a.c * ((a.R[3 * k] * x + a.R[3 * k + 1] * y) + a.R[3 * k + 2] * z) + a.t[k];
+}
+
+struct MomentsArgs {
+  const double* cur;          // [N,3]
+  const double* ref;          // [M,3] in ORIGINAL order
+  const long long* index;     // [N]
+  const double* d2;           // [N]
+  long long N, M, blocks;     // blocks = ceil(N / 256): the rows of partials
+  double trim2, origin[3];
+  double* partials;           // [blocks,17]
+  double* out;                // [17]
+  unsigned long long* counters;      // [2]: matched, bad_index (the 16 bytes behind out's 17 doubles)
+};
+
+// red[e][j] += red[e][j + s] for s = 128 ... 1: td_odom.hip's block_reduce with the slot as the slow axis, so that the threads of a
+// wave touch consecutive doubles (no bank conflict at any s >= 16).  The sums land in red[e][0].
+__device__ __forceinline__ void moments_tree(double (*red)[TD_THREADS], const double* v) {
+  const int j = threadIdx.x;
+#pragma unroll
+  for (int e = 0; e < TD_ICP_SLOTS; ++e) red[e][j] = v[e];
+  __syncthreads();
+  for (int s = TD_THREADS / 2; s > 0; s >>= 1) {
+    if (j < s) {
+#pragma unroll
+      for (int e = 0; e < TD_ICP_SLOTS; ++e) red[e][j] += red[e][j + s];
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(TD_THREADS) void icp_moments_rows_kernel(const MomentsArgs a) {
+  __shared__ double red[TD_ICP_SLOTS][TD_THREADS];      // 34 816 bytes: four workgroups (16 waves) per CU of 160 KiB
+  __shared__ unsigned cnt[2];
+  if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * TD_THREADS + threadIdx.x;
+  double v[TD_ICP_SLOTS];
+#pragma unroll
+  for (int e = 0; e < TD_ICP_SLOTS; ++e) v[e] = 0.0;
+  if (i < a.N) {
+    const long long j = a.index[i];
+    const double d2 = a.d2[i];
+    if (j >= a.M || j < -1) {
+      atomicAdd(&cnt[1], 1u);      // LDS; nothing is read through such an index
+    } else if (j >= 0 && d2 <= a.trim2) {      // a NaN fails
+      atomicAdd(&cnt[0], 1u);
+      double p[3], q[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        p[k] = a.cur[i * 3 + k] - a.origin[k];
+        q[k] = a.ref[j * 3 + k] - a.origin[k];
+        v[k] = p[k];
+        v[3 + k] = q[k];
+      }
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[6 + 3 * r + c] = q[r] * p[c];
+      v[15] = (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2];
+      v[16] = d2;
+    }
+  }
+  moments_tree(red, v);
+  if (threadIdx.x < TD_ICP_SLOTS) a.partials[(long long)blockIdx.x * TD_ICP_SLOTS + threadIdx.x] = red[threadIdx.x][0];
+  if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(a.counters + threadIdx.x, (unsigned long long)cnt[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(TD_THREADS) void icp_moments_finish_kernel(const MomentsArgs a) {
+  __shared__ double red[TD_ICP_SLOTS][TD_THREADS];
+  double v[TD_ICP_SLOTS];
+#pragma unroll
+  for (int e = 0; e < TD_ICP_SLOTS; ++e) v[e] = 0.0;
+  for (long long k = threadIdx.x; k < a.blocks; k += TD_THREADS) {
+#pragma unroll
+    for (int e = 0; e < TD_ICP_SLOTS; ++e) v[e] += a.partials[k * TD_ICP_SLOTS + e];
+  }
+  moments_tree(red, v);
+  if (threadIdx.x < TD_ICP_SLOTS) a.out[threadIdx.x] = red[threadIdx.x][0];
+}
+
+static inline bool all_finite(const double* v, int n) {
+  for (int k = 0; k < n; ++k)
+    if (!isfinite(v[k])) return false;
+  return true;
+}
+
+}  // namespace td
+
+extern "C" int td_cloud_transform(const double* src, long long N, double c, const double* R, const double* t, double* out,
+                                  td_stream_t stream) {
+  if (!src || !out || !R || !t || N < 0 || !isfinite(c) || !td::all_finite(R, 9) || !td::all_finite(t, 3)) return TD_ERR_BAD_ARG;
+  if (N == 0) return TD_OK;
+  td::TransformArgs a;
+  a.src = src; a.out = out; a.N = N; a.c = c;
+  for (int k = 0; k < 9; ++k) a.R[k] = R[k];
+  for (int k = 0; k < 3; ++k) a.t[k] = t[k];
+  const unsigned blocks = td::blocks_1d(N);
+  if (!blocks) return TD_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(td::cloud_transform_kernel, dim3(blocks), dim3(TD_THREADS), 0, (hipStream_t)stream, a);
+  return td::record_launch_error(hipGetLastError(), "td_cloud_transform");
+}
+
+extern "C" long long td_icp_moments_workspace(long long N) {
+  if (N <= 0) return 0;
+  return ((N + TD_THREADS - 1) / TD_THREADS) * TD_ICP_SLOTS * (long long)sizeof(double);
+}
+
+extern "C" int td_icp_moments(const double* cur, long long N, const double* ref, long long M, const long long* index, const double* d2,
+                              double trim2, const double* origin, void* workspace, long long workspace_bytes, double* out,
+                              td_stream_t stream) {
+  if (!out || !origin || N < 0 || M < 0 || !(trim2 >= 0.0) || !td::all_finite(origin, 3) || workspace_bytes < 0 ||
+      (N > 0 && (!cur || !index || !d2 || !workspace)) || (N > 0 && M > 0 && !ref) || !td::aligned_to(out, 8) ||
+      !td::aligned_to(workspace, 8))
+    return TD_ERR_BAD_ARG;
+  if (workspace_bytes < td_icp_moments_workspace(N)) return TD_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  // the 17 sums and the two counters start from zero: N = 0 ends here, with out zeroed
+  const hipError_t e = hipMemsetAsync(out, 0, (TD_ICP_SLOTS + 2) * sizeof(double), st);
+  if (e != hipSuccess) return td::record_launch_error(e, "td_icp_moments (clear)");
+  if (N == 0) return TD_OK;
+  td::MomentsArgs a;
+  a.cur = cur; a.ref = ref; a.index = index; a.d2 = d2; a.N = N; a.M = M;
+  a.trim2 = trim2;
+  for (int k = 0; k < 3; ++k) a.origin[k] = origin[k];
+  a.partials = static_cast<double*>(workspace); a.out = out;
+  a.counters = reinterpret_cast<unsigned long long*>(out + TD_ICP_SLOTS);
+  const unsigned blocks = td::blocks_1d(N);
+  if (!blocks) return TD_ERR_UNSUPPORTED;
+  a.blocks = blocks;
+  hipLaunchKernelGGL(td::icp_moments_rows_kernel, dim3(blocks), dim3(TD_THREADS), 0, st, a);
+  const int rc = td::record_launch_error(hipGetLastError(), "td_icp_moments (rows)");
+  if (rc != TD_OK) return rc;
+  hipLaunchKernelGGL(td::icp_moments_finish_kernel, dim3(1), dim3(TD_THREADS), 0, st, a);
+  return td::record_launch_error(hipGetLastError(), "td_icp_moments (finish)");
+}

@@ -137,6 +137,11 @@ SIGNATURES = {
                           ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
     "td_nn_query": (_I, [_P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, ctypes.c_double,
                          ctypes.POINTER(ctypes.c_double), _I, _P, _P, _P, _P]),
+    "td_cloud_transform": (_I, [_P, ctypes.c_longlong, ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                _P, _P]),
+    "td_icp_moments_workspace": (ctypes.c_longlong, [ctypes.c_longlong]),
+    "td_icp_moments": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, ctypes.c_double, ctypes.POINTER(ctypes.c_double), _P,
+                            ctypes.c_longlong, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
