@@ -970,6 +970,57 @@ long long td_icp_moments_workspace(long long N);
 int td_icp_moments(const double* cur, long long N, const double* ref, long long M, const long long* index, const double* d2, double trim2,
                    const double* origin, void* workspace, long long workspace_bytes, double* out, td_stream_t stream);
 
+/*
+ * Point-to-plane alignment: surface normals of a cloud (csrc/td_normals.hip, tripled_amd/cloud_normals.py) and the sums of the
+ * linearised point-to-plane step (csrc/td_align.hip, tripled_amd/cloud_align.py, criterion="plane").  The statements are
+ * cloud_normals.normals_numpy and cloud_align.plane_moments_numpy, which the kernels equal bit for bit.  float64, every product and
+ * sum rounded on its own; no floating-point atomics, no kernel waits on another workgroup.
+ *
+ * td_cloud_normals: one launch, one thread per query.
+ *   query [N,3] float64;  points [M,3] float64, cell_key [C] int64, cell_start [C+1] int64: a cloud sorted into td_nn_query's grid
+ *   for `tau` (cloud_eval.grid_hip; `order` is not needed; points and cell_key may be NULL with M = 0, C = 0);  radius in (0, tau];
+ *   Q = 2^18 / radius, divided ONCE by the caller;  min_neighbours >= 3;  max_curvature >= 0 (+inf: nothing is rough).
+ *   The query walks the 27 cells around it like td_nn_query.  For every grid point p with e = p - query and
+ *   ((e_x e_x) + (e_y e_y)) + (e_z e_z) <= radius radius (a NaN fails): n += 1, i_k = (int64) rint(e_k Q) (half to even),
+ *   S1_k += i_k, S2_kl += i_k i_l for k <= l: ten 64-bit integer sums, independent of every order.  Then in float64
+ *     m_k = double(S1_k) / double(n),  C_kl = double(S2_kl) / double(n) - m_k m_l,
+ *   C is diagonalised by cyclic Jacobi over (0,1), (0,2), (1,2) with 4 sweeps, never fewer (a rotation whose off-diagonal is exactly 0
+ *   is skipped; theta = (a_qq - a_pp) / (2 a_pq), t = sign(theta) / (|theta| + sqrt(theta theta + 1)), c = 1 / sqrt(t t + 1), s = t c;
+ *   the update formulas are cloud_normals.py's docstring), the normal is the eigenvector column of the smallest diagonal entry (lowest
+ *   index among equal ones) divided by sqrt(((x x) + (y y)) + (z z)), its sign chosen so that the component of largest magnitude is
+ *   positive (lowest index among ties); curvature = max(lambda_min, 0) / ((l0 + l1) + l2).
+ *   normal [N,3] float64 (out): +0.0 in all three when the query has none;  curvature [N] float64 (out): +inf when undefined;
+ *   count [N] int64 (out): n, 0 for an invalid query;  counters [5] int64, INCREMENTED (LDS first, then one 64-bit atomic per workgroup
+ *   and counter), every query in exactly one, the first that holds: [4] invalid (not finite or outside the key range, as in
+ *   td_nn_query), [1] few (n < min_neighbours), [2] degenerate (trace not > 0, middle eigenvalue not > 0, or anything not finite),
+ *   [3] rough (curvature > max_curvature: the curvature is written, the normal is not), [0] valid.
+ *   TD_ERR_BAD_ARG before any launch: a null query, cell_start or output, N, M or C < 0, C > M, tau not positive and finite, radius
+ *     outside (0, tau], Q radius not within 2^-32 of 2^18 (Q is not 2^18 / radius to rounding), min_neighbours < 3, max_curvature not >= 0, points null with M > 0, cell_key null
+ *     with C > 0.  TD_ERR_UNSUPPORTED: M >= 2^26 (with |i_k| <= 2^18 + 1 no sum can overflow below that).  N = 0 is a successful
+ *     no-op without a launch.
+ *
+ * td_icp_plane_moments: td_icp_moments' contract (two launches, the same two-stage tree, the order of the sums depends on N alone)
+ *   with one more input, normals [M,3] float64 in the reference's ORIGINAL order (NULL allowed with M = 0), and 37 slots.
+ *   Row i is matched iff 0 <= index_i < M, d2_i <= trim2 (a NaN fails) and normals[index_i] is not all zero; a row that passes the
+ *   first two tests and whose neighbour has no normal is counted as no_normal.  With p = cur_i - origin, q = ref[j] - origin,
+ *   n = normals[j], g = p - q:
+ *     a = (p_y n_z - p_z n_y,  p_z n_x - p_x n_z,  p_x n_y - p_y n_x,  n_x,  n_y,  n_z,  (p_x n_x + p_y n_y) + p_z n_z)
+ *     r = (n_x g_x + n_y g_y) + n_z g_z
+ *   and a matched row contributes, in this order,  a_i a_j for i <= j, row-major (28),  a_i r (7),  r r,  d2_i;  any other row +0.0.
+ *   workspace: td_icp_plane_moments_workspace(N) bytes (37 float64 per workgroup of stage 1; 0 for N = 0), 8-byte aligned
+ *     (TD_ERR_WORKSPACE if workspace_bytes is less)
+ *   out: 40 x 8 bytes (out): the 37 sums as float64, then matched, bad_index and no_normal as int64.  All 40 are cleared first,
+ *     also for N = 0, which launches nothing else.
+ *   TD_ERR_BAD_ARG before any launch: as td_icp_moments, and normals null with N > 0 and M > 0.
+ */
+int td_cloud_normals(const double* query, long long N, const double* points, long long M, const long long* cell_key,
+                     const long long* cell_start, long long C, double tau, double radius, double Q, long long min_neighbours,
+                     double max_curvature, double* normal, double* curvature, long long* count, long long* counters, td_stream_t stream);
+long long td_icp_plane_moments_workspace(long long N);
+int td_icp_plane_moments(const double* cur, long long N, const double* ref, const double* normals, long long M, const long long* index,
+                         const double* d2, double trim2, const double* origin, void* workspace, long long workspace_bytes, double* out,
+                         td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@ reference has no such program.
          [--config CFG | --K fx fy cx cy] [--height H --width W] [--ref_voxel V] [--min_depth Z] [--max_range R] [--tau T] \
          [--thresholds T1 T2 ...] [--pred_scale S] [--batch_size 12] [--save_ref ref.ply] [--save_error error.ply] [--device cpu] \
          [--align {none,rigid,similarity} [--align_tau T] [--align_iters 30] [--align_trim D] [--align_stride 1] [--init_poses FILE] \
-          [--save_transform T.txt] [--save_aligned aligned.ply]]
+          [--align_criterion {point,plane}] [--save_transform T.txt] [--save_aligned aligned.ply]] \
+         [--align_normal_radius R] [--align_min_neighbours 6] [--align_max_curvature 0.01] [--align_rcond 1e-3] [--save_ref_normals FILE]
 
 Scans: <data_path>/sequences/NN/velodyne/%06d.bin (float32 x y z reflectance), velodyne to camera from the "Tr:" line of
 <data_path>/sequences/NN/calib.txt.  --poses: camera-to-world poses in KITTI pose text, one per scan of the sequence, typically the
@@ -25,6 +26,13 @@ radius of the correspondence search (default 2 tau), --align_trim leaves out cor
 --align_stride uses every n-th point, --align_iters bounds the passes; all UNTUNED.  Prints the initial guess, one line per pass
 (matched, rms), the final scale, R, t and whether it converged; the score lines are then prefixed "aligned".  --save_transform writes
 the 4x4 [[c R, t], [0, 1]] as text, --save_aligned the aligned cloud with its colours.
+--align_criterion plane minimises the distance along the REFERENCE'S NORMALS instead (point to plane: two clouds that sample the same
+surfaces at different points; tripled_amd.cloud_normals, csrc/td_normals.hip): the normals are estimated once from the neighbours within
+--align_normal_radius (default and at most --align_tau), a point with fewer than --align_min_neighbours of them or a patch rougher than
+--align_max_curvature (lambda_min / trace) has none and is not matched; a direction whose eigenvalue is below --align_rcond of the
+largest is dropped from the step and reported (the translation along a corridor); all UNTUNED.  It prints the normal counters once and
+per pass additionally the rms along the normals and the rank.  --save_ref_normals writes the reference cloud with these normals as
+nx ny nz (all zero: none), with or without --align; a --ref file without colours or counts gets black and 1.
 Prints the scan statistics, one line per cause; both clouds' sizes, dropped points and largest cell; one line per threshold with
 precision, recall and F-score; accuracy and completeness (the mean distance to the nearest neighbour, capped at tau).
 --save_error writes the predicted cloud coloured by min(distance, tau) / tau through the magma table, pure green (0, 255, 0) where
@@ -41,7 +49,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tripled_amd  # noqa: F401,E402
-from tripled_amd import cloud, cloud_align, cloud_eval, odometry, velodyne  # noqa: E402
+from tripled_amd import cloud, cloud_align, cloud_eval, cloud_normals, odometry, velodyne  # noqa: E402
 
 
 def _host(t):
@@ -70,10 +78,20 @@ def _align(args, pred_xyz, ref_xyz):
     align_tau = 2.0 * args.tau if args.align_tau is None else args.align_tau
     print("-> Aligning (%s, tau %.6g, at most %d passes, stride %d)" % (args.align, align_tau, args.align_iters, args.align_stride))
     print("initial scale %.9g R %s t %s" % (init[0], " ".join("%.9g" % v for v in np.reshape(init[1], -1)), " ".join("%.9g" % v for v in init[2])))
-    aligner = cloud_align.CloudAligner(args.device, align_tau, args.align, args.align_iters, args.align_trim, args.align_stride)
+    aligner = cloud_align.CloudAligner(args.device, align_tau, args.align, args.align_iters, args.align_trim, args.align_stride,
+                                       criterion=args.align_criterion, normal_radius=args.align_normal_radius,
+                                       min_neighbours=args.align_min_neighbours, max_curvature=args.align_max_curvature, rcond=args.align_rcond)
     result = aligner.align(pred_xyz, ref_xyz, init)
+    if args.align_criterion == "plane":
+        print("reference normals: " + " ".join("%s %d" % item for item in aligner.normal_stats.items()))
     for n, (matched, rms) in enumerate(result.history):
-        print("pass %d: matched %d rms %.6g" % (n, matched, rms))
+        line = "pass %d: matched %d rms %.6g" % (n, matched, rms)
+        if args.align_criterion == "plane":
+            plane_rms, rank, dropped = aligner.plane_history[n]
+            line += " plane rms %.6g rank %d" % (plane_rms, rank)
+            if dropped is not None:
+                line += " dropped " + "; ".join(" ".join("%.3f" % v for v in row) for row in dropped)
+        print(line)
     print("scale %.9g R %s t %s" % (result.scale, " ".join("%.9g" % v for v in result.R.reshape(-1)), " ".join("%.9g" % v for v in result.t)))
     print("converged %s after %d passes" % (result.converged, result.iterations))
     if args.save_transform:
@@ -116,9 +134,17 @@ def main():
     ap.add_argument("--init_poses", default=None, help="the poses the cloud was fused with; aligned to --poses for the initial guess")
     ap.add_argument("--save_transform", default=None, help="the 4x4 [[c R, t], [0, 1]] as text")
     ap.add_argument("--save_aligned", default=None, help="the aligned cloud (PLY)")
+    ap.add_argument("--align_criterion", choices=cloud_align.CRITERIA, default="point", help="plane: the distance along the reference's normals")
+    ap.add_argument("--align_normal_radius", type=float, default=None, help="neighbourhood of a normal (default: align_tau, untuned)")
+    ap.add_argument("--align_min_neighbours", type=int, default=6, help="fewer neighbours: no normal (untuned)")
+    ap.add_argument("--align_max_curvature", type=float, default=0.01, help="a rougher patch (lambda_min / trace): no normal (untuned)")
+    ap.add_argument("--align_rcond", type=float, default=1e-3, help="eigenvalues below this fraction of the largest are dropped (untuned)")
+    ap.add_argument("--save_ref_normals", default=None, help="the reference cloud with nx ny nz (PLY)")
     args = ap.parse_args()
     if args.align == "none" and (args.init_poses or args.save_transform or args.save_aligned):
         ap.error("--init_poses, --save_transform and --save_aligned need --align rigid or similarity")
+    if args.align == "none" and args.align_criterion != "point":
+        ap.error("--align_criterion needs --align rigid or similarity")
     if args.init_poses and not args.poses:
         ap.error("--init_poses needs --poses, the trajectory it is aligned to")
     if (args.ref is None) == (args.data_path is None):
@@ -129,7 +155,8 @@ def main():
         ap.error("at most one of --config and --K")
     pred_xyz, pred = _load_xyz(args.cloud)
     if args.ref:
-        ref_xyz, _ = _load_xyz(args.ref)
+        ref_xyz, saved = _load_xyz(args.ref)
+        ref_rgb = ref_count = None                   # read from ``saved`` where they are needed, if it has them
         print("-> Reference cloud %s: %d points" % (args.ref, len(ref_xyz)))
     else:
         K, height, width = None, 0, 0
@@ -162,11 +189,24 @@ def main():
         ref = fuser.fuse(scans, poses[numbers])
         for name, value in ref.stats.items():
             print("scans %s %d" % (name, value))
-        ref_xyz = ref.xyz
+        ref_xyz, ref_rgb, ref_count = ref.xyz, ref.rgb, ref.count
         if args.save_ref:
             os.makedirs(os.path.dirname(os.path.abspath(args.save_ref)), exist_ok=True)
             cloud.save_ply(args.save_ref, ref.xyz, ref.rgb, ref.count)
             print("saved %d reference points to %s" % (len(ref.keys), args.save_ref))
+    if args.save_ref_normals:
+        align_tau = 2.0 * args.tau if args.align_tau is None else args.align_tau
+        estimator = cloud_normals.CloudNormals(args.device, align_tau, args.align_normal_radius, args.align_min_neighbours, args.align_max_curvature)
+        found = estimator.estimate(ref_xyz)
+        if ref_rgb is None:                          # a reference PLY may hold x y z alone: black, and one sample per point
+            names, n = saved.dtype.names, len(saved)
+            has_rgb = all(c in names for c in ("red", "green", "blue"))
+            ref_rgb = np.stack([saved["red"], saved["green"], saved["blue"]], 1) if has_rgb else np.zeros((n, 3), np.uint8)
+            ref_count = saved["count"] if "count" in names else np.ones(n, np.int32)
+        os.makedirs(os.path.dirname(os.path.abspath(args.save_ref_normals)), exist_ok=True)
+        cloud.save_ply(args.save_ref_normals, ref_xyz, ref_rgb, ref_count, normals=_host(found.normal))
+        print("saved %d reference points with normals to %s: %s" % (len(_host(ref_xyz)), args.save_ref_normals,
+                                                                    " ".join("%s %d" % item for item in found.stats.items())))
     label, pred_scale = "", args.pred_scale
     if args.align != "none":
         pred_xyz = _align(args, pred_xyz, ref_xyz)

@@ -16,8 +16,17 @@ Timed, median of ``--repeats`` after ``--warmup`` runs of the same shapes:
 Alongside: the passes it took, the recovered transform's distance from the planted one, and ``device_equals_numpy``: on a stated random
 subsample of the predicted points against the whole reference, the bits of the transformed points and, after nearest_numpy, of the 17
 sums and the counters.
+With ``--criterion plane`` additionally (the point-to-point figures stay, for the comparison):
+  normals          td_cloud_normals (csrc/td_normals.hip) of the whole reference against its own grid, device events, and its counters
+  plane_moments    td_icp_plane_moments as called, with its ratio to ``moments`` and its bytes per row (64 + 24 for the gathered normal)
+  plane_iteration  one pass of CloudAligner(criterion="plane"): transform, query, plane moments, the copy of 40 numbers, the host solve
+  plane_align      CloudAligner(criterion="plane").align end to end (grid, origin, normals, all passes), host clock
+  plane_result     its passes, ranks, dropped directions (the weight of every unknown: w (3), tau (3), sigma), its distance from the
+                   planted transform and the largest displacement of a predicted point from its planted position, beside ``result``'s
+  plane_device_equals_numpy   on the subsample: the bits of the normals (subsampled queries, whole grid), of the 37 sums and the counters
+Every figure is of ONE run of this tool (``runs``: 1) on a SYNTHETIC scene (``scene``).
 
-  python tools/cloud_align_bench.py [--repeats 20] [--warmup 3] [--length 2000] [--subsample 20000] [--json profiles/cloud_eval/cloud_align_bench.json]
+  python tools/cloud_align_bench.py [--repeats 20] [--warmup 3] [--length 2000] [--subsample 20000] [--criterion plane] [--json profiles/cloud_eval/cloud_align_bench.json]
 """
 import argparse
 import json
@@ -34,11 +43,12 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import tripled_amd  # noqa: F401,E402
-from tripled_amd import cloud_align, cloud_eval  # noqa: E402
+from tripled_amd import cloud_align, cloud_eval, cloud_normals  # noqa: E402
 from cloud_eval_bench import TAU, VOXEL, street, timed, wall_clock  # noqa: E402
 
 DEGREES, SCALE, SHIFT = 0.01, 1.0002, 0.1
 ROW_BYTES = 64          # per row of the moments: 24 (cur) + 8 (index) + 8 (d2) read in order, 24 gathered from the reference
+PLANE_ROW_BYTES = 88    # the plane moments gather the neighbour's normal as well: 24 more
 
 
 def rotation(axis, degrees):
@@ -70,11 +80,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--length", type=float, default=2000.0)
     ap.add_argument("--subsample", type=int, default=20000)
+    ap.add_argument("--criterion", choices=cloud_align.CRITERIA, default="point")
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     device = torch.device("cuda", 0)
     out = {"device": torch.cuda.get_device_name(0), "voxel": VOXEL, "tau": TAU, "repeats": args.repeats, "warmup": args.warmup,
-           "length": args.length, "planted": {"degrees": DEGREES, "scale": SCALE, "shift": SHIFT}}
+           "length": args.length, "planted": {"degrees": DEGREES, "scale": SCALE, "shift": SHIFT}, "runs": 1,
+           "scene": "SYNTHETIC street (tools/cloud_eval_bench.py)", "criterion": args.criterion}
     ref, moved = street(args.length, 1, 0.0, 0.0), street(args.length, 2, 0.5 * VOXEL, 0.1)
     centre = np.array([0.5 * args.length, 0.0, 0.0])
     R = rotation([0.3, 1.0, 0.2], DEGREES)
@@ -133,6 +145,50 @@ def main():
     bits = lambda a: np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
     out["device_equals_numpy"] = bool(np.array_equal(bits(got_cur.cpu().numpy()), bits(want_cur)) and
                                       np.array_equal(bits(got[0]), bits(want[0])) and got[1:] == want[1:])
+    if args.criterion == "plane":
+        displacement = lambda res: float(np.sqrt((((res.scale * pred[pick].dot(res.R.T) + res.t) - (SCALE * pred[pick].dot(R.T) + t)) ** 2).sum(1)).max())
+        out["result"]["max_displacement_subsample"] = displacement(result)
+        counters = torch.zeros(5, dtype=torch.int64, device=device)
+        found = cloud_normals.normals_hip(ref_d, grid, stats=counters)
+        out["normals"] = timed(lambda: cloud_normals.normals_hip(ref_d, grid), args.warmup, args.repeats)
+        out["normal_counters"] = dict(zip(cloud_normals.CAUSES, (int(v) for v in counters.cpu().numpy())))
+        out["normals_max_cell"] = grid.stats["max_cell"]
+        plane_sums = torch.empty(40, dtype=torch.float64, device=device)
+        plane = lambda: cloud_align.plane_moments_hip(cur, ref_d, found.normal, nb.index, nb.d2, trim2, origin, out=plane_sums)
+        out["plane_moments"] = timed(plane, args.warmup, args.repeats)
+        out["plane_moments_over_moments"] = out["plane_moments"]["median_us"] / out["moments"]["median_us"]
+        out["plane_moments_bytes_per_row"] = PLANE_ROW_BYTES
+        out["plane_moments_bytes_per_s"] = PLANE_ROW_BYTES * len(pred) / (out["plane_moments"]["median_us"] * 1e-6)
+        first = cloud_align.plane_moments_to_host(plane_sums)
+        out["plane_matched_first_pass"], out["plane_no_normal_first_pass"] = first[1], first[3]
+        planar = cloud_align.CloudAligner(device, TAU, criterion="plane")
+        length = float((0.5 * (ref.max(0) - ref.min(0))).max())
+
+        def one_plane_pass():
+            m, matched, _, _ = planar._pass(pred_d, ref_d, grid, origin, 1.0, eye, zero, trim2, found.normal)
+            return cloud_align.solve_plane_step(matched, m, True, length, planar.rcond)
+
+        out["plane_iteration"] = wall_clock(one_plane_pass, args.warmup, args.repeats)
+        out["plane_align"] = wall_clock(lambda: planar.align(pred_d, ref_d), args.warmup, args.repeats)
+        res = planar.align(pred_d, ref_d)
+        out["plane_result"] = {"iterations": res.iterations, "converged": res.converged, "matched": [h[0] for h in res.history],
+                               "rms": [h[1] for h in res.history], "plane_rms": [h[0] for h in planar.plane_history],
+                               "ranks": [h[1] for h in planar.plane_history],
+                               "dropped_weights": [None if h[2] is None else (h[2] ** 2).tolist() for h in planar.plane_history],
+                               "unknowns": ["w_x", "w_y", "w_z", "tau_x", "tau_y", "tau_z", "sigma"],
+                               "scale_error": abs(res.scale - SCALE) / SCALE, "R_error": float(np.abs(res.R - R).max()),
+                               "t_error": float(np.abs(res.t - t).max()), "t_error_xyz": np.abs(res.t - t).tolist(),
+                               "max_displacement_subsample": displacement(res)}
+        want_normals = cloud_normals.normals_numpy(ref[pick], host_grid)
+        got_normals = cloud_normals.normals_hip(ref_d[torch.from_numpy(pick).to(device)].contiguous(), grid)
+        host_normals = found.normal.cpu().numpy()
+        want_plane = cloud_align.plane_moments_numpy(want_cur, ref, host_normals, want_nb.index, want_nb.d2, trim2, origin)
+        got_plane = cloud_align.plane_moments_to_host(cloud_align.plane_moments_hip(got_cur, ref_d, found.normal, got_nb.index, got_nb.d2, trim2, origin))
+        out["plane_device_equals_numpy"] = bool(
+            np.array_equal(bits(got_normals.normal.cpu().numpy()), bits(want_normals.normal)) and
+            np.array_equal(bits(got_normals.curvature.cpu().numpy()), bits(want_normals.curvature)) and
+            np.array_equal(got_normals.count.cpu().numpy(), want_normals.count) and
+            np.array_equal(bits(got_plane[0]), bits(want_plane[0])) and got_plane[1:] == want_plane[1:])
     line = json.dumps(out)
     print(line)
     if args.json:

@@ -342,19 +342,28 @@ def fuse_numpy(depth, color, poses, inv_K, voxel=DEFAULT_VOXEL, stride=1, border
     return Cloud(xyz[keep], rgb[keep], count[keep], keys[keep], _stats(counts, len(keys), int(keep.sum()), dropped))
 
 
-def save_ply(path, xyz, rgb, count):
-    """binary_little_endian 1.0 PLY: x y z float, red green blue uchar, count int; one structured array, one write."""
+def save_ply(path, xyz, rgb, count, normals=None):
+    """binary_little_endian 1.0 PLY: x y z float, red green blue uchar, count int; one structured array, one write.  ``normals`` [n,3]
+    (cloud_normals'; all zero: the point has none) adds nx ny nz float after count; without it the file is what it always was."""
     xyz, rgb, count = (np.asarray(t.cpu() if torch.is_tensor(t) else t) for t in (xyz, rgb, count))
     n = len(xyz)
     if xyz.shape != (n, 3) or rgb.shape != (n, 3) or count.shape != (n,):
         raise ValueError("xyz [n,3], rgb [n,3], count [n]; got %s, %s, %s" % (xyz.shape, rgb.shape, count.shape))
-    rec = np.empty(n, PLY_DTYPE)
+    dtype = PLY_DTYPE
+    if normals is not None:
+        normals = np.asarray(normals.cpu() if torch.is_tensor(normals) else normals)
+        if normals.shape != (n, 3):
+            raise ValueError("normals [n,3], got %s" % (normals.shape,))
+        dtype = np.dtype(PLY_DTYPE.descr + [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")])
+    rec = np.empty(n, dtype)
     rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
     rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
     rec["count"] = count
+    if normals is not None:
+        rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % n]
-    header += ["property %s %s" % ({"<f4": "float", "u1": "uchar", "<i4": "int"}[PLY_DTYPE[name].str.replace("|", "")], name)
-               for name in PLY_DTYPE.names]
+    header += ["property %s %s" % ({"<f4": "float", "u1": "uchar", "<i4": "int"}[dtype[name].str.replace("|", "")], name)
+               for name in dtype.names]
     with open(path, "wb") as f:
         f.write(("\n".join(header + ["end_header"]) + "\n").encode("ascii"))
         f.write(rec.tobytes())

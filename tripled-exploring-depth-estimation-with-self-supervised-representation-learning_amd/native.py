@@ -142,6 +142,11 @@ SIGNATURES = {
     "td_icp_moments_workspace": (ctypes.c_longlong, [ctypes.c_longlong]),
     "td_icp_moments": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, ctypes.c_double, ctypes.POINTER(ctypes.c_double), _P,
                             ctypes.c_longlong, _P, _P]),
+    "td_cloud_normals": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, ctypes.c_double, ctypes.c_double,
+                              ctypes.c_double, ctypes.c_longlong, ctypes.c_double, _P, _P, _P, _P, _P]),
+    "td_icp_plane_moments_workspace": (ctypes.c_longlong, [ctypes.c_longlong]),
+    "td_icp_plane_moments": (_I, [_P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_double,
+                                  ctypes.POINTER(ctypes.c_double), _P, ctypes.c_longlong, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
