@@ -17,7 +17,8 @@ SHAPES = [
     (12, 48, 160, 64, 64, 1),       # layer1 conv2 (ResNet50) / BasicBlock convs (ResNet18)
     (12, 24, 80, 128, 128, 1),      # layer2
     (12, 12, 40, 256, 256, 1),      # layer3
-    (12, 6, 20, 512, 512, 1),       # layer4: 20-pixel rows (four row crossings per stage)
+    (12, 6, 20, 512, 512, 1),       # layer4: 20-pixel rows (three row crossings per stage: stages start at multiples of 64, so at a
+                                    # column wo0 that is a multiple of 4, and wo0 + 63 <= 79 < 4 * 20 -- four are not reachable)
     (24, 24, 80, 128, 128, 1),      # pose encoder, two stacked pairs
     (12, 6, 20, 512, 256, 0),       # DepthDecoder.iconv4 on the reflection-padded map (8 x 22 input)
     (12, 24, 80, 256, 256, 0),      # DepthDecoder.merge2
