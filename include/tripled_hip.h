@@ -1021,6 +1021,55 @@ int td_icp_plane_moments(const double* cur, long long N, const double* ref, cons
                          const double* d2, double trim2, const double* origin, void* workspace, long long workspace_bytes, double* out,
                          td_stream_t stream);
 
+/*
+ * Surfel rendering (csrc/td_surfel.hip, tripled_amd/cloud_normals.py, tripled_amd/render.py): normals oriented towards the nearest
+ * camera, and a cloud drawn as oriented discs in space.  The reference has no such program: the statements are
+ * cloud_normals.orient_numpy and render.render_surfels_numpy, which the kernels equal bit for bit.  float64, every product, sum and
+ * quotient rounded on its own; integer atomics only; no kernel waits on another workgroup.
+ *
+ * td_normals_orient: one fill and one launch, one thread per point, the camera centres staged through LDS 256 at a time (any C).
+ *   xyz [V,3] float32, normal [V,3] float32 (all three components zero: the point has none), poses [C,3,4] float64 camera-to-world,
+ *   all on the device.  Per point p, with centre_c = pose_scale t_c and w = centre_c - (double)p:
+ *     d2_c = ((w_x w_x) + (w_y w_y)) + (w_z w_z);  the viewpoint is the c of the smallest d2_c, the lowest c among equal ones; a NaN
+ *     never wins;  s = ((n_x w_x) + (n_y w_y)) + (n_z w_z) with the winner's w;  the normal is negated (exactly) when s < 0.
+ *   out_normal [V,3] float32 (out);  camera [V] int32 (out): the winner, -1 when every distance is a NaN;  stats [4] int64 (out, set):
+ *   flipped, kept (s >= 0), none (no normal: copied as it is, the camera is still written), invalid (no camera won, or s is a NaN:
+ *   the normal is copied as it is).  Every point is in exactly one.
+ *   TD_ERR_BAD_ARG before any launch: a null or misaligned pointer, V < 0, C <= 0.  V = 0 clears the stats and launches nothing.
+ *
+ * td_cloud_render_surfels: two fills and two launches (one with V = 0), td_cloud_render's inputs, workspace
+ *   (td_cloud_render_workspace_bytes) and table, plus normal [V,3] float32, radius > 0 (the disc's, in the cloud's units), cull 0/1,
+ *   ambient in [0, 1] and form (0: the library's choice, 1: one thread per surfel, 2: boxes of more than 4 pixels go through an LDS
+ *   queue and are rasterised by a wave each; all forms return the same bits).  K: K10 must be 0 and K00, K11 positive.
+ *   Per point i and camera c, with e, q_0, q_1, z = q_2 as in td_cloud_render:
+ *     m_k = (R_0k n_0 + R_1k n_1) + R_2k n_2;  a point without a normal gets m = (0, 0, -1) (a billboard)
+ *     out of range unless z_near <= z <= z_far;  culled (cull = 1) when ((m_0 q_0) + (m_1 q_1)) + (m_2 z) > 0, orthographic m_2 > 0
+ *     perspective:  u = ((K00 q_0 + K01 q_1) + K02 z) / z;  v = (K11 q_1 + K12 z) / z;  tm = max(z_near, z - radius);  g = radius / tm;
+ *                   a_x = g (1 + |q_0| / z);  a_y = g (1 + |q_1| / z);  b_x = K00 a_x + |K01| a_y;  b_y = K11 a_y
+ *     orthographic: u = (K00 q_0 + K01 q_1) + K02;  v = K11 q_1 + K12;  b_x = (K00 + |K01|) radius;  b_y = K11 radius
+ *     ui = rint(u), vi = rint(v);  r = floor(max(b_x, b_y) + (1/2 + 2^-10));  capped when r > 16, then r = 16 (TD_SURFEL_MAX)
+ *     outside unless ui + r >= 0, ui - r <= W-1, vi + r >= 0, vi - r <= H-1 (a NaN fails);  else drawn
+ *   Per pixel (x, y) of the box [ui-r, ui+r] x [vi-r, vi+r] inside the image:
+ *     d_1 = (y - K12) / K11;  d_0 = ((x - K02) - K01 d_1) / K00
+ *     perspective:  den = ((m_0 d_0) + (m_1 d_1)) + m_2;  num = ((m_0 q_0) + (m_1 q_1)) + (m_2 z);  t = num / den;  hit = (t d_0, t d_1, t)
+ *     orthographic: den = m_2;  num = ((m_0 (q_0 - d_0)) + (m_1 (q_1 - d_1))) + (m_2 z);  t = num / den;  hit = (d_0, d_1, t)
+ *     covered when den < 0 or den > 0, ((e_0 e_0) + (e_1 e_1)) + (e_2 e_2) <= radius radius for e = hit - q, and z_near <= t <= z_far;
+ *     a covered pixel takes the minimum of its entry and (bits of (float)t) << 32 | i
+ *   depth, index, color: as td_cloud_render, the depth being (float)t;  normal_map [C,3,H,W] float32 (out): (float)m of the winner,
+ *   negated when den > 0, +0.0 where nothing was drawn;  the colour is the point's own when ambient = 1, else per channel
+ *   min(255, floor(c (ambient + (1 - ambient) shade) + 0.5)) with shade = |den| / sqrt(((d_0 d_0) + (d_1 d_1)) + 1) (orthographic: / sqrt(1)).
+ *   stats [C,8] int64 (out), in this order: points, out_of_range, outside (the box misses the image), culled, capped, billboards,
+ *   drawn, pixels_hit;  points = out_of_range + culled + outside + drawn;  capped and billboards count drawn surfels.
+ *   TD_ERR_BAD_ARG before any launch: td_cloud_render's causes, a null normal or normal_map, radius not positive and finite, ambient
+ *   outside [0, 1], form outside 0 ... 2, K not finite, K10 != 0, K00 or K11 not positive.  TD_ERR_UNSUPPORTED: as td_cloud_render.
+ */
+int td_normals_orient(const float* xyz, const float* normal, long long V, const double* poses, int C, double pose_scale,
+                      float* out_normal, int* camera, long long* stats, td_stream_t stream);
+int td_cloud_render_surfels(const float* xyz, const uint8_t* rgb, const float* normal, long long V, const double* poses, const double* K,
+                            int C, int H, int W, double pose_scale, double z_near, double z_far, double radius, int ortho, int cull,
+                            double ambient, int form, int bg_r, int bg_g, int bg_b, void* workspace, long long workspace_bytes,
+                            float* depth, uint8_t* color, int* index, float* normal_map, long long* stats, td_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

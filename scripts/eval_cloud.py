@@ -32,7 +32,10 @@ surfaces at different points; tripled_amd.cloud_normals, csrc/td_normals.hip): t
 --align_max_curvature (lambda_min / trace) has none and is not matched; a direction whose eigenvalue is below --align_rcond of the
 largest is dropped from the step and reported (the translation along a corridor); all UNTUNED.  It prints the normal counters once and
 per pass additionally the rms along the normals and the rank.  --save_ref_normals writes the reference cloud with these normals as
-nx ny nz (all zero: none), with or without --align; a --ref file without colours or counts gets black and 1.
+nx ny nz (all zero: none), with or without --align; a --ref file without colours or counts gets black and 1.  With --orient_normals
+the written normals are first turned towards the nearest camera of --poses (the poses the scans were fused under; with --ref give the
+--poses the reference was fused under; cloud_normals.orient_*, csrc/td_surfel.hip) and the counters of that are printed; the alignment
+itself keeps the unoriented normals (the plane criterion is sign-free, and an alignment must not change).
 Prints the scan statistics, one line per cause; both clouds' sizes, dropped points and largest cell; one line per threshold with
 precision, recall and F-score; accuracy and completeness (the mean distance to the nearest neighbour, capped at tau).
 --save_error writes the predicted cloud coloured by min(distance, tau) / tau through the magma table, pure green (0, 255, 0) where
@@ -140,11 +143,14 @@ def main():
     ap.add_argument("--align_max_curvature", type=float, default=0.01, help="a rougher patch (lambda_min / trace): no normal (untuned)")
     ap.add_argument("--align_rcond", type=float, default=1e-3, help="eigenvalues below this fraction of the largest are dropped (untuned)")
     ap.add_argument("--save_ref_normals", default=None, help="the reference cloud with nx ny nz (PLY)")
+    ap.add_argument("--orient_normals", action="store_true", help="turn the saved normals towards the nearest camera of --poses")
     args = ap.parse_args()
     if args.align == "none" and (args.init_poses or args.save_transform or args.save_aligned):
         ap.error("--init_poses, --save_transform and --save_aligned need --align rigid or similarity")
     if args.align == "none" and args.align_criterion != "point":
         ap.error("--align_criterion needs --align rigid or similarity")
+    if args.orient_normals and not (args.save_ref_normals and args.poses):
+        ap.error("--orient_normals needs --save_ref_normals and --poses")
     if args.init_poses and not args.poses:
         ap.error("--init_poses needs --poses, the trajectory it is aligned to")
     if (args.ref is None) == (args.data_path is None):
@@ -197,7 +203,12 @@ def main():
     if args.save_ref_normals:
         align_tau = 2.0 * args.tau if args.align_tau is None else args.align_tau
         estimator = cloud_normals.CloudNormals(args.device, align_tau, args.align_normal_radius, args.align_min_neighbours, args.align_max_curvature)
-        found = estimator.estimate(ref_xyz)
+        if args.orient_normals:
+            view_poses = odometry.load_kitti_poses(args.poses)
+            a, _, b = (args.frames or ":").partition(":")
+            found = estimator.estimate(ref_xyz, poses=view_poses[int(a or 0):int(b or len(view_poses))])
+        else:
+            found = estimator.estimate(ref_xyz)
         if ref_rgb is None:                          # a reference PLY may hold x y z alone: black, and one sample per point
             names, n = saved.dtype.names, len(saved)
             has_rgb = all(c in names for c in ("red", "green", "blue"))

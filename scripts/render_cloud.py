@@ -4,7 +4,8 @@ and no checkpoint are needed.  The reference has no such program.
 
   python scripts/render_cloud.py --cloud cloud.ply --poses poses.txt [--frames A:B] [--every N] \
          (--config config/cfg_kitti_tripleD.py | --K fx fy cx cy) [--height H --width W] [--near Z] [--far Z] [--splat S] \
-         [--pose_scale S] [--top] [--save_depth] [--device cpu] --out DIR
+         [--pose_scale S] [--top] [--save_depth] [--device cpu] --out DIR \
+         [--surfels [--surfel_radius R] [--cull] [--ambient A] [--save_normals]]
 
 --poses: camera-to-world poses in KITTI pose text (reconstruct.py --save_poses writes the ones a cloud was fused with; with the
 ground truth give the --pose_scale the cloud was fused with).  --frames A:B takes the poses A ... B-1, --every N every N-th of them.
@@ -17,6 +18,17 @@ and the largest depth drawn, black where nothing was drawn), with --save_depth v
 drawn), and with --top top_color.png / top_depth.png: the cloud from above, orthographic, the sequence's forward direction up.  Prints
 the statistics per view and, last, the mean share of pixels hit.  The work is tripled_amd.render.CloudRenderer (csrc/td_render.hip on
 a HIP device).
+--surfels draws every point as an oriented disc in space instead (tripled_amd.render.CloudRenderer.render_surfels, csrc/td_surfel.hip):
+a surface sampled more densely than --surfel_radius (the cloud's units; default: the --splat default, untuned) has no holes and hides
+what is behind it, and the depth is that of the ray's hit on the disc.  The normals are the PLY's nx ny nz if it has them, else they are
+estimated on the spot (tripled_amd.cloud_normals.CloudNormals: --normal_tau, --normal_radius, --min_neighbours, --max_curvature, untuned);
+either way they are turned towards the nearest camera of --poses (all of them, not only --frames) before drawing, and the counters of
+that are printed.  A point without a normal is a disc facing the camera.  --cull skips discs that show their back, --ambient A < 1
+shades the colours by the angle between normal and ray (1: the colours as they are).  Also written: view_%06d_normal.png (the
+camera-space normal, turned towards the viewer, from [-1, 1] to [0, 255]; black where nothing was drawn) and with --save_normals
+view_%06d_normal.npy (float32 [3,H,W]).  --top works the same way through the orthographic camera.  Limits: one radius for all
+discs, the nearest disc wins a pixel (no blending), a disc's pixel box is capped at 33 x 33 (counted as capped), and the nearest camera
+is only a guess at the side a surface was seen from.
 """
 import argparse
 import os
@@ -29,7 +41,7 @@ from PIL import Image
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tripled_amd  # noqa: F401,E402
-from tripled_amd import cloud, infer, odometry, render  # noqa: E402
+from tripled_amd import cloud, cloud_eval, cloud_normals, infer, odometry, render  # noqa: E402
 
 
 def depth_picture(depth):
@@ -47,6 +59,44 @@ def save_view(out_dir, stem, depth, color, save_depth=False):
     Image.fromarray(depth_picture(depth)).save(os.path.join(out_dir, stem + "_depth.png"))
     if save_depth:
         np.save(os.path.join(out_dir, stem + "_depth.npy"), depth)
+
+
+def normal_picture(normal, index):
+    """float32 [3,H,W], int32 [H,W] -> uint8 [H,W,3]: [-1, 1] to [0, 255], black where nothing was drawn."""
+    picture = np.clip(np.floor((normal.transpose(1, 2, 0).astype(np.float64) + 1.0) * 127.5 + 0.5), 0, 255).astype(np.uint8)
+    picture[index < 0] = 0
+    return picture
+
+
+def save_surfel_view(out_dir, stem, out, j, save_depth, save_normals):
+    save_view(out_dir, stem, out.depth[j], out.color[j], save_depth)
+    Image.fromarray(normal_picture(out.normal[j], out.index[j])).save(os.path.join(out_dir, stem + "_normal.png"))
+    if save_normals:
+        np.save(os.path.join(out_dir, stem + "_normal.npy"), out.normal[j])
+
+
+def surfel_stats_line(name, stats, pixels):
+    return "%s %s share_hit %.4f" % (name, " ".join("%s %d" % (k, v) for k, v in zip(render.SURFEL_STATS, stats)), stats[7] / pixels)
+
+
+def oriented_normals(args, points, xyz, poses):
+    """The PLY's normals or estimated ones, turned towards the nearest camera -> float32 [V,3] on the host."""
+    if all(c in points.dtype.names for c in ("nx", "ny", "nz")):
+        normals = np.stack([points["nx"], points["ny"], points["nz"]], 1).astype(np.float32)
+        print("normals: the cloud's own, %d points without" % int(np.count_nonzero(~normals.any(1))))
+    else:
+        found = cloud_normals.CloudNormals(args.device, args.normal_tau, args.normal_radius, args.min_neighbours, args.max_curvature).estimate(xyz)
+        normals = np.asarray(found.normal.cpu() if torch.is_tensor(found.normal) else found.normal).astype(np.float32)
+        print("normals: estimated, " + " ".join("%s %d" % item for item in found.stats.items()))
+    if torch.device(args.device).type == "cuda":
+        dev = torch.device(args.device)
+        turned = cloud_normals.orient_hip(torch.from_numpy(xyz).to(dev), torch.from_numpy(normals).to(dev),
+                                          torch.from_numpy(np.ascontiguousarray(poses)).to(dev), args.pose_scale)
+        turned = cloud_normals.Oriented(*(t.cpu().numpy() for t in turned))
+    else:
+        turned = cloud_normals.orient_numpy(xyz, normals, poses, args.pose_scale)
+    print("orientation: " + " ".join("%s %d" % (k, v) for k, v in zip(cloud_normals.ORIENT_STATS, turned.stats)))
+    return turned.normal
 
 
 def stats_line(name, stats, pixels):
@@ -72,6 +122,15 @@ def main():
     ap.add_argument("--batch_size", type=int, default=12)
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--out", required=True)
+    ap.add_argument("--surfels", action="store_true", help="draw oriented discs in space instead of squares in the image")
+    ap.add_argument("--surfel_radius", type=float, default=render.DEFAULT_SPLAT, help="the discs' radius in the cloud's units (untuned)")
+    ap.add_argument("--cull", action="store_true", help="skip discs that show their back")
+    ap.add_argument("--ambient", type=float, default=1.0, help="1: the colours as they are; below: shaded by the normal (untuned)")
+    ap.add_argument("--save_normals", action="store_true")
+    ap.add_argument("--normal_tau", type=float, default=2.0 * cloud_eval.DEFAULT_TAU, help="grid cell of the normal estimation (untuned)")
+    ap.add_argument("--normal_radius", type=float, default=None, help="neighbourhood of a normal (default: normal_tau, untuned)")
+    ap.add_argument("--min_neighbours", type=int, default=6, help="fewer neighbours: no normal (untuned)")
+    ap.add_argument("--max_curvature", type=float, default=0.01, help="a rougher patch (lambda_min / trace): no normal (untuned)")
     args = ap.parse_args()
     if (args.config is None) == (args.K is None):
         ap.error("one of --config and --K")
@@ -106,20 +165,36 @@ def main():
     print("-> Drawing %d points into %d views of %d x %d" % (len(xyz), len(numbers), height, width))
     shares = []
     resident = renderer.upload(xyz, rgb)                          # once; a batch of views at a time is held on the host
+    surfel = None
+    if args.surfels:
+        normals = oriented_normals(args, points, xyz, poses)
+        surfel = dict(radius=args.surfel_radius, cull=args.cull, ambient=args.ambient)
     for at in range(0, len(numbers), args.batch_size):
         batch = numbers[at:at + args.batch_size]
-        out = renderer.render(*resident, poses[batch])
+        if surfel:
+            out = renderer.render_surfels(*resident, normals, poses[batch], **surfel)
+        else:
+            out = renderer.render(*resident, poses[batch])
         for j, n in enumerate(batch):
-            save_view(args.out, "view_%06d" % n, out.depth[j], out.color[j], args.save_depth)
-            print(stats_line("view %06d" % n, out.stats[j], height * width))
-            shares.append(out.stats[j, 4] / (height * width))
+            if surfel:
+                save_surfel_view(args.out, "view_%06d" % n, out, j, args.save_depth, args.save_normals)
+                print(surfel_stats_line("view %06d" % n, out.stats[j], height * width))
+            else:
+                save_view(args.out, "view_%06d" % n, out.depth[j], out.color[j], args.save_depth)
+                print(stats_line("view %06d" % n, out.stats[j], height * width))
+            shares.append(out.stats[j, -1] / (height * width))
     if args.top:
         pose, top_K = render.top_view(xyz, height, width, near=args.near)
         finite = xyz[np.isfinite(xyz).all(1)]
         far = 3.0 * args.near + float(finite[:, 1].max() - finite[:, 1].min())        # the lowest point is at 2 near + the box's height
-        out = renderer.render(*resident, pose[None], K=top_K, ortho=True, far=far, pose_scale=1.0)
-        save_view(args.out, "top", out.depth[0], out.color[0])
-        print(stats_line("top", out.stats[0], height * width))
+        if surfel:
+            out = renderer.render_surfels(*resident, normals, pose[None], K=top_K, ortho=True, far=far, pose_scale=1.0, **surfel)
+            save_surfel_view(args.out, "top", out, 0, False, args.save_normals)
+            print(surfel_stats_line("top", out.stats[0], height * width))
+        else:
+            out = renderer.render(*resident, pose[None], K=top_K, ortho=True, far=far, pose_scale=1.0)
+            save_view(args.out, "top", out.depth[0], out.color[0])
+            print(stats_line("top", out.stats[0], height * width))
     print("mean share of pixels hit %.4f over %d views" % (float(np.mean(shares)), len(shares)))
 
 

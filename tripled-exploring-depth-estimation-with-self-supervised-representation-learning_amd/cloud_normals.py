@@ -38,7 +38,19 @@ three components are +0.0; the curvature is +inf where it is undefined (invalid,
 SWEEPS = 4 is the smallest count at which the normals of the seeded test clouds agree with numpy.linalg.eigh's eigenvector within 1e-12
 (sine of the angle) wherever (l1 - l0) / trace >= 1e-6 (tests/test_cloud_plane_cpu.py; DESIGN 25 has the figures).
 
-Limits: the normal has no orientation (towards a viewpoint or otherwise) beyond the sign convention; the covariance is of coordinates
+Orientation (``orient_numpy``, ``orient_bruteforce``, ``orient_hip``: td_normals_orient in csrc/td_surfel.hip).  Given the poses the cloud
+was fused under, every normal is turned towards the camera centre nearest to its point.  Per point p (float32, widened) and camera c,
+float64, every operation rounded on its own:
+    centre_c = pose_scale t_c;   w = centre_c - p;   d2_c = ((w_x w_x) + (w_y w_y)) + (w_z w_z)
+    the viewpoint is the c of the smallest d2_c, the lowest c among equal ones; a NaN distance never wins (camera -1 when none did)
+    s = ((n_x w_x) + (n_y w_y)) + (n_z w_z) with the winner's w;   the normal is negated (exactly) when s < 0, kept when s >= 0
+Every point ends in exactly one class: none (no normal, all three components zero: it stays +0.0, its nearest camera is still
+reported), invalid (no camera won, or s is a NaN: the normal stays as it is), flipped, kept.  Orienting twice changes nothing.
+LIMIT of the viewpoint rule: the fused cloud keeps no record of which frame saw a voxel.  The nearest camera on the trajectory is on
+the seen side of any surface the trajectory did not pass through; where the trajectory passes on both sides of a thin surface, or a
+surface was seen from far away while the trajectory later came near its back, the sign can be wrong.
+
+Limits: without poses the normal has no orientation beyond the sign convention; the covariance is of coordinates
 quantised to radius 2^-18; a fixed radius, no k-nearest; the defaults min_neighbours = 6 and max_curvature = 0.01 are UNTUNED.
 """
 import collections
@@ -54,6 +66,8 @@ SWEEPS = 4                            # csrc/td_normals.hip: TD_NORMALS_SWEEPS
 QUANT = 2.0 ** 18                     # csrc/td_normals.hip: the host passes Q = QUANT / radius
 MAX_POINTS = 1 << 26                  # grid points: below it the integer sums cannot overflow
 CAUSES = ("valid", "few", "degenerate", "rough", "invalid")
+ORIENT_STATS = ("flipped", "kept", "none", "invalid")
+ORIENT_CHUNK = 256                    # csrc/td_surfel.hip: camera centres staged through LDS at a time
 PAIRS = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
 
 Normals = collections.namedtuple("Normals", "normal curvature count stats")
@@ -335,6 +349,102 @@ def normals_hip(query, grid, radius=None, min_neighbours=6, max_curvature=0.01, 
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# orientation towards the nearest camera
+
+Oriented = collections.namedtuple("Oriented", "normal camera stats")
+Oriented.__doc__ = """normal float32 [V,3], camera int32 [V] (the nearest camera, -1 where none won), stats int64 [4] in the order of
+ORIENT_STATS: flipped, kept, none, invalid."""
+
+
+def _orient_inputs(xyz, normal, poses):
+    xyz = np.ascontiguousarray(xyz, dtype=np.float32)
+    normal = np.ascontiguousarray(normal, dtype=np.float32)
+    poses = np.asarray(poses, dtype=np.float64)
+    if poses.ndim == 3 and poses.shape[1:] == (4, 4):
+        poses = poses[:, :3]
+    poses = np.ascontiguousarray(poses)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or normal.shape != xyz.shape or poses.ndim != 3 or poses.shape[1:] != (3, 4) or not len(poses):
+        raise ValueError("xyz [V,3], normal [V,3], poses [C,3,4] with C >= 1; got %s, %s, %s" % (xyz.shape, normal.shape, poses.shape))
+    return xyz, normal, poses
+
+
+def orient_numpy(xyz, normal, poses, pose_scale=1.0):
+    """xyz, normal float32 [V,3], poses float64 [C,3,4] camera-to-world -> Oriented of numpy arrays.  The statement td_normals_orient is
+    tested against: one pass over the cameras in ascending order, vectorised over the points."""
+    xyz, normal, poses = _orient_inputs(xyz, normal, poses)
+    V, ps = len(xyz), np.float64(pose_scale)
+    p = [xyz[:, k].astype(np.float64) for k in range(3)]
+    camera = np.full(V, -1, np.int32)
+    best, w = np.zeros(V), [np.zeros(V) for _ in range(3)]
+    with np.errstate(all="ignore"):
+        for c in range(len(poses)):
+            d = [ps * poses[c, k, 3] - p[k] for k in range(3)]
+            d2 = ((d[0] * d[0]) + (d[1] * d[1])) + (d[2] * d[2])
+            win = (d2 == d2) & ((camera < 0) | (d2 < best))
+            camera[win] = c
+            best = np.where(win, d2, best)
+            w = [np.where(win, d[k], w[k]) for k in range(3)]
+        n = [normal[:, k].astype(np.float64) for k in range(3)]
+        s = ((n[0] * w[0]) + (n[1] * w[1])) + (n[2] * w[2])
+    none = (normal[:, 0] == 0) & (normal[:, 1] == 0) & (normal[:, 2] == 0)
+    invalid = ~none & ((camera < 0) | (s != s))
+    flipped = ~none & ~invalid & (s < 0.0)
+    kept = ~none & ~invalid & ~flipped
+    out = np.where(flipped[:, None], -normal, normal).astype(np.float32)
+    stats = np.array([np.count_nonzero(m) for m in (flipped, kept, none, invalid)], np.int64)
+    return Oriented(out, camera, stats)
+
+
+def orient_bruteforce(xyz, normal, poses, pose_scale=1.0):
+    """orient_numpy said a second time: one point at a time, Python floats, a plain loop over the cameras.  For the tests."""
+    xyz, normal, poses = _orient_inputs(xyz, normal, poses)
+    out, camera, stats = normal.copy(), np.full(len(xyz), -1, np.int32), [0, 0, 0, 0]
+    centres = [[float(np.float64(pose_scale) * poses[c, k, 3]) for k in range(3)] for c in range(len(poses))]
+    for i in range(len(xyz)):
+        px, py, pz = (float(v) for v in xyz[i])
+        cam, best, w = -1, 0.0, (0.0, 0.0, 0.0)
+        for c, (cx, cy, cz) in enumerate(centres):
+            dx, dy, dz = cx - px, cy - py, cz - pz
+            d2 = ((dx * dx) + (dy * dy)) + (dz * dz)
+            if d2 == d2 and (cam < 0 or d2 < best):
+                cam, best, w = c, d2, (dx, dy, dz)
+        camera[i] = cam
+        nx, ny, nz = (float(v) for v in normal[i])
+        if nx == 0.0 and ny == 0.0 and nz == 0.0:
+            stats[2] += 1
+            continue
+        s = ((nx * w[0]) + (ny * w[1])) + (nz * w[2])
+        if cam < 0 or s != s:
+            stats[3] += 1
+        elif s < 0.0:
+            stats[0] += 1
+            out[i] = -normal[i]
+        else:
+            stats[1] += 1
+    return Oriented(out, camera, np.array(stats, np.int64))
+
+
+def orient_hip(xyz, normal, poses, pose_scale=1.0):
+    """orient_numpy as one launch of td_normals_orient -> Oriented of device tensors.  xyz, normal float32 [V,3], poses float64
+    [C,3,4], all on one HIP device; a CPU tensor is an error.  No synchronisation."""
+    native.load()
+    native.require_device(xyz, normal, poses)
+    if xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3 or normal.dtype != torch.float32 or tuple(normal.shape) != tuple(xyz.shape) \
+            or poses.dtype != torch.float64 or poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4) or poses.shape[0] < 1:
+        raise ValueError("xyz float32 [V,3], normal float32 [V,3], poses float64 [C,3,4] with C >= 1; got %s %s, %s %s, %s %s" % (
+            tuple(xyz.shape), xyz.dtype, tuple(normal.shape), normal.dtype, tuple(poses.shape), poses.dtype))
+    V, dev = xyz.shape[0], poses.device
+    out = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    camera = torch.empty(V, dtype=torch.int32, device=dev)
+    stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    if V == 0:                           # an empty tensor has no pointer to pass
+        return Oriented(out, camera, stats)
+    native.call("td_normals_orient", xyz.contiguous(), normal.contiguous(), V, poses.contiguous(), poses.shape[0], float(pose_scale), out,
+                camera, stats)
+    return Oriented(out, camera, stats)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 
 class CloudNormals:
     """estimate(xyz) -> Normals in the cloud's own order: the grid is built from the cloud and every point is a query into it.
@@ -343,7 +453,11 @@ class CloudNormals:
                 arrays are device tensors; 'cpu': grid_numpy and normals_numpy.  The two paths agree on the bits.
     tau         the cell size of the grid;  radius: the neighbourhood, inside (0, tau], default tau
     min_neighbours, max_curvature   a point with fewer neighbours (itself included) or a rougher patch gets no normal; UNTUNED
-    stats is a dict of Python ints under the names of CAUSES."""
+    stats is a dict of Python ints under the names of CAUSES.
+
+    estimate(xyz, poses=...) also orients the normals towards the nearest camera (module docstring): the points and the normals go
+    through orient_numpy / orient_hip rounded to float32, which is what a PLY holds, and a normal that came back negated is negated in
+    float64.  stats then also holds "orient_flipped", "orient_kept", "orient_none", "orient_invalid"."""
 
     def __init__(self, device, tau, radius=None, min_neighbours=6, max_curvature=0.01):
         self.device = torch.device(device)
@@ -355,8 +469,9 @@ class CloudNormals:
         if not (0 < self.radius <= self.tau) or int(min_neighbours) != min_neighbours or min_neighbours < 3 or not self.max_curvature >= 0:
             raise ValueError("0 < radius <= tau, min_neighbours >= 3, max_curvature >= 0; got %r, %r, %r" % (radius, min_neighbours, max_curvature))
 
-    def estimate(self, xyz, grid=None):
-        """``grid``: the cloud's Grid when the caller has built it already (for this tau, on this path)."""
+    def estimate(self, xyz, grid=None, poses=None, pose_scale=1.0):
+        """``grid``: the cloud's Grid when the caller has built it already (for this tau, on this path).  ``poses``: [C,3,4] or
+        [C,4,4] camera-to-world, None: the normals keep the sign convention."""
         if not self.on_hip:
             x = cloud_eval._xyz64(xyz, "xyz")
             grid = cloud_eval.grid_numpy(x, self.tau) if grid is None else grid
@@ -370,4 +485,19 @@ class CloudNormals:
             grid = cloud_eval.grid_hip(x, self.tau) if grid is None else grid
             out = normals_hip(x, grid, self.radius, self.min_neighbours, self.max_curvature)
             counters = out.stats.cpu().numpy()
-        return Normals(out.normal, out.curvature, out.count, {name: int(v) for name, v in zip(CAUSES, counters)})
+        stats = {name: int(v) for name, v in zip(CAUSES, counters)}
+        normal = out.normal
+        if poses is not None:
+            if not self.on_hip:
+                n32 = normal.astype(np.float32)
+                turned = orient_numpy(x.astype(np.float32), n32, poses, pose_scale)
+                normal = np.where((turned.normal != n32).any(1)[:, None], -normal, normal)
+                orient = turned.stats
+            else:
+                poses = _orient_inputs(np.zeros((0, 3)), np.zeros((0, 3)), poses.cpu().numpy() if torch.is_tensor(poses) else poses)[2]
+                n32 = normal.to(torch.float32)
+                turned = orient_hip(x.to(torch.float32), n32, torch.from_numpy(poses).to(self.device), pose_scale)
+                normal = torch.where((turned.normal != n32).any(1)[:, None], -normal, normal)
+                orient = turned.stats.cpu().numpy()
+            stats.update({"orient_" + name: int(v) for name, v in zip(ORIENT_STATS, orient)})
+        return Normals(normal, out.curvature, out.count, stats)

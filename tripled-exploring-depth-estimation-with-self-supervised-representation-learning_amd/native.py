@@ -147,6 +147,10 @@ SIGNATURES = {
     "td_icp_plane_moments_workspace": (ctypes.c_longlong, [ctypes.c_longlong]),
     "td_icp_plane_moments": (_I, [_P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_double,
                                   ctypes.POINTER(ctypes.c_double), _P, ctypes.c_longlong, _P, _P]),
+    "td_normals_orient": (_I, [_P, _P, ctypes.c_longlong, _P, _I, ctypes.c_double, _P, _P, _P, _P]),
+    "td_cloud_render_surfels": (_I, [_P, _P, _P, ctypes.c_longlong, _P, ctypes.POINTER(ctypes.c_double), _I, _I, _I, ctypes.c_double,
+                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _I, ctypes.c_double, _I, _I, _I, _I, _P,
+                                     ctypes.c_longlong, _P, _P, _P, _P, _P, _P]),
 }
 
 DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
