@@ -68,6 +68,37 @@ def half_way_cloud(radius=0.5):
     return cloud, Q
 
 
+KEY_RANGE_TAU = 1.0
+KEY_RANGE_STATS = [412, 3, 0, 0, 188]            # valid, few, degenerate, rough, invalid of key_range_scene at radius = tau, 3, 1.0
+
+
+def key_range_scene():
+    """(query float64 [603,3], ref float64 [6004,3]) for tau = 1: test_hip_cloud_eval.py's scene of cells at both ends of the key range
+    (per axis a point sits near +2^20, near -2^20 or in the middle), denser, so that patches have neighbours.  The last cell on an
+    axis starts at 2^20 - 2^-20, a neighbour cell beyond either end does not exist, a point beyond either is dropped from the grid
+    and a query there is invalid.  ref ends in three points of the all-top corner cell, whose key is the sentinel (dropped), and one
+    in the cell below it; query ends in two queries in the corner cell and one below it (valid: served from the cells around)."""
+    edge = float(2 ** 20)
+    rng = np.random.default_rng(9)
+
+    def around(n):
+        base = rng.uniform(-1.5, 1.5, (n, 3))
+        side = rng.integers(0, 4, (n, 3))                              # per axis: the top edge, the bottom edge, or the middle
+        return base + np.where(side == 0, edge, np.where(side == 1, -edge, 0.0)) + np.where(side == 1, -0.5, 0.0)
+
+    ref = np.concatenate([around(6000), np.full((3, 3), edge + 0.25), [[edge + 0.25, edge + 0.25, edge - 0.5]]])
+    query = np.concatenate([around(600), np.full((2, 3), edge + 0.3), [[edge + 0.3, edge + 0.3, edge - 0.3]]])
+    return query, ref
+
+
+def check_key_range_grid(grid, stats):
+    """The grid of key_range_scene's ref reaches both ends of the key range, and the classes valid, few and invalid all occur."""
+    ix = np.stack(cloud.unpack_key(np.asarray(grid.cell_key)), -1)
+    assert ix.max() == cloud.HALF - 1 and ix.min() == -cloud.HALF
+    assert grid.stats["dropped"] == 1965 and grid.stats["cells"] == 694
+    assert np.asarray(stats).tolist() == KEY_RANGE_STATS and stats[0] > 0 and stats[1] > 0 and stats[4] > 0
+
+
 # ---- plane moments -------------------------------------------------------------------------------------------------------------------
 
 def plane_correspondences(N, M=97, seed=0, kind="mixed"):

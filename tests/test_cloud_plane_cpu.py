@@ -70,6 +70,16 @@ def test_normals_are_the_all_pairs_loop(N):
         assert got.count.max() == 300 and grid.stats["max_cell"] == 300 and grid.stats["dropped"] == 4
 
 
+def test_normals_in_cells_at_both_ends_of_the_key_range():
+    """td_cloud_normals walks the grid as td_nn_query does: the same scene as test_hip_cloud_eval.py's test of that name."""
+    query, ref = P.key_range_scene()
+    tau = P.KEY_RANGE_TAU
+    grid = cloud_eval.grid_numpy(ref, tau)
+    got = cloud_normals.normals_numpy(query, grid, tau, 3, 1.0)
+    assert _same_normals(got, cloud_normals.normals_bruteforce(query, ref, tau, tau, 3, 1.0))
+    P.check_key_range_grid(grid, got.stats)
+
+
 def test_normals_do_not_depend_on_the_order_inside_a_cell():
     x = P.poison_cloud(1000)
     grid = cloud_eval.grid_numpy(x, P.NORMAL_TAU)

@@ -76,6 +76,19 @@ def test_normals_are_the_numpy_statement(N):
         assert _h(got.count).max() == 300 and (want.stats > 0).all()
 
 
+def test_normals_in_cells_at_both_ends_of_the_key_range():
+    """The scene of the CPU test of that name, which the all-pairs loop pins there."""
+    query, ref = P.key_range_scene()
+    tau = P.KEY_RANGE_TAU
+    host_grid = cloud_eval.grid_numpy(ref, tau)
+    want = cloud_normals.normals_numpy(query, host_grid, tau, 3, 1.0)
+    grid = cloud_eval.grid_hip(_d(ref), tau)
+    got = cloud_normals.normals_hip(_d(query), grid, tau, 3, 1.0)
+    assert _same(got, want)
+    P.check_key_range_grid(grid._replace(cell_key=_h(grid.cell_key)), _h(got.stats))      # the grid that was queried
+    P.check_key_range_grid(host_grid, want.stats)
+
+
 def test_no_queries_the_exact_radius_and_half_way_offsets():
     x = P.poison_cloud(65)
     grid = cloud_eval.grid_hip(_d(x), P.NORMAL_TAU)

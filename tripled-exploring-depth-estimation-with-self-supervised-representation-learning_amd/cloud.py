@@ -53,7 +53,7 @@ import torch
 from . import infer, native, odometry
 
 HALF = 1 << 20                       # voxel coordinates lie in [-2^20, 2^20)
-INVALID_KEY = (1 << 63) - 1          # csrc/td_cloud.hip: TD_CLOUD_INVALID; the sort puts it last
+INVALID_KEY = (1 << 63) - 1          # csrc/td_grid.h: TD_KEY_INVALID; the sort puts it last
 CAUSES = ("valid", "invalid_stride", "invalid_border", "invalid_depth", "invalid_edge", "invalid_range")
 
 # Starting values in the MODEL's units: the stereo baseline (0.54 m) is 0.015 of them and the evaluation multiplies depths by 36, so
@@ -80,13 +80,34 @@ _PLY_TYPES = {"float": "<f4", "float32": "<f4", "uchar": "u1", "uint8": "u1", "i
 # ---------------------------------------------------------------------------------------------------------------------------
 # host statements
 
+def _pack(ix, iy, iz):
+    """pack_key without its check, on int64 numpy arrays or tensors."""
+    return ((ix + HALF) << 42) | ((iy + HALF) << 21) | (iz + HALF)
+
+
 def pack_key(ix, iy, iz):
     """Voxel coordinates in [-2^20, 2^20) -> int64 key (ascending key order = x major, then y, then z)."""
     ix, iy, iz = (np.asarray(v, dtype=np.int64) for v in (ix, iy, iz))
     for v in (ix, iy, iz):
         if v.size and (v.min() < -HALF or v.max() >= HALF):
             raise ValueError("voxel coordinates: [-2^20, 2^20)")
-    return ((ix + HALF) << 42) | ((iy + HALF) << 21) | (iz + HALF)
+    return _pack(ix, iy, iz)
+
+
+def grid_keys_numpy(g):
+    """g: the three float64 arrays of grid coordinates (world inv_voxel, or a point times inv_cell) -> (key int64, ok bool, offset
+    uint64), csrc/td_grid.h's voxel_key: i = floor(g), ok where every i lies in [-2^20, 2^20) (a NaN fails both
+    comparisons), key = INVALID_KEY where not ok and for the one corner voxel whose key is the sentinel, offset = q_x | q_y << 10 |
+    q_z << 20 with q = min(1023, int(floor((g - i) 1024.0))), 0 where the key is invalid."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        f = [np.floor(v) for v in g]
+        ok = np.ones(np.shape(f[0]), bool)
+        for v in f:
+            ok &= (v >= -float(HALF)) & (v < float(HALF))
+        key = np.where(ok, _pack(*(np.where(ok, v, 0.0).astype(np.int64) for v in f)), INVALID_KEY).astype(np.int64)
+        q = [np.minimum(1023, np.where(key != INVALID_KEY, np.floor((v - i) * 1024.0), 0.0).astype(np.int64)).astype(np.uint64)
+             for v, i in zip(g, f)]
+    return key, ok, q[0] | (q[1] << np.uint64(10)) | (q[2] << np.uint64(20))
 
 
 def unpack_key(key):
@@ -199,23 +220,14 @@ def keys_numpy(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_
                 bad |= inside & (~np.isfinite(nb) | (np.abs(d - nb) > e * np.minimum(d, nb)))
             mark(bad, 4)
         px, py, pz = camera_points_numpy(d, m, depth_scale)
-        g, f = [], []
+        g = []
         for k in range(3):
             r0, r1, r2, t = (P[:, k, j].reshape(B, 1, 1) for j in range(4))
             world = ((r0 * px + r1 * py) + r2 * pz) + pose_scale * t
             g.append(world * inv_voxel)
-            f.append(np.floor(g[k]))
-        inside = np.ones(d.shape, bool)
-        for k in range(3):
-            inside &= (f[k] >= -float(HALF)) & (f[k] < float(HALF))          # a NaN fails both
-        mark(~inside, 5)
-        ok = cause == 0
-        i = [np.where(ok, f[k], 0.0).astype(np.int64) + HALF for k in range(3)]
-        key = (i[0] << 42) | (i[1] << 21) | i[2]
-        mark(ok & (key == INVALID_KEY), 5)                                   # the one corner voxel whose key is the sentinel
-        ok = cause == 0
-        q = [np.minimum(1023, np.where(ok, np.floor((g[k] - f[k]) * 1024.0), 0.0).astype(np.int64)).astype(np.uint64) for k in range(3)]
-    payload = q[0] | (q[1] << np.uint64(10)) | (q[2] << np.uint64(20))
+    key, _, payload = grid_keys_numpy(g)
+    mark(key == INVALID_KEY, 5)
+    ok = cause == 0
     for ch, shift in ((0, 30), (1, 38), (2, 46)):
         payload = payload | (c[:, ch].astype(np.uint64) << np.uint64(shift))
     key = np.where(ok, key, INVALID_KEY).astype(np.int64).reshape(-1)

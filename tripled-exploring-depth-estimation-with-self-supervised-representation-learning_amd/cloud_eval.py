@@ -128,37 +128,27 @@ def scan_keys_numpy(points, offsets, Tr, poses, K=None, height=0, width=0, min_d
             u = ((K9[0] * cx + K9[1] * cy) + K9[2] * cz) / cz
             v = ((K9[3] * cx + K9[4] * cy) + K9[5] * cz) / cz
             mark(~((u >= 0) & (u <= W - 1) & (v >= 0) & (v <= H - 1)), 3)                       # a NaN fails
-        g, f = [], []
+        g = []
         for k in range(3):
             r0, r1, r2, t = (P[sc, k, j] for j in range(4))
             g.append((((r0 * cx + r1 * cy) + r2 * cz) + t) * inv_voxel)
-            f.append(np.floor(g[k]))
-        inside = np.ones(n, bool)
-        for k in range(3):
-            inside &= (f[k] >= -float(HALF)) & (f[k] < float(HALF))                             # a NaN fails both
-        mark(~inside, 4)
-        ok = cause == 0
-        c = [np.where(ok, f[k], 0.0).astype(np.int64) + HALF for k in range(3)]
-        key = (c[0] << 42) | (c[1] << 21) | c[2]
-        mark(ok & (key == INVALID_KEY), 4)                                                      # the one corner voxel
-        ok = cause == 0
-        q = [np.minimum(1023, np.where(ok, np.floor((g[k] - f[k]) * 1024.0), 0.0).astype(np.int64)).astype(np.uint64) for k in range(3)]
         grey = np.floor(pts[:, 3].astype(np.float64) * 255.0 + 0.5)
         grey = np.where(grey >= 0, np.minimum(grey, 255.0), 0.0).astype(np.uint64)              # a NaN reflectance is 0
-    payload = q[0] | (q[1] << np.uint64(10)) | (q[2] << np.uint64(20)) | (grey << np.uint64(30)) | (grey << np.uint64(38)) | \
-        (grey << np.uint64(46))
+    key, _, payload = cloud.grid_keys_numpy(g)
+    mark(key == INVALID_KEY, 4)
+    ok = cause == 0
+    payload = payload | (grey << np.uint64(30)) | (grey << np.uint64(38)) | (grey << np.uint64(46))
     key = np.where(ok, key, INVALID_KEY).astype(np.int64)
     payload = np.where(ok, payload, np.uint64(0)).astype(np.uint64)
     return key, payload, np.bincount(cause, minlength=5).astype(np.int64)
 
 
 def _cells_numpy(x, ic):
-    """float64 [M,3] -> (cell key int64 [M], ok bool [M]): floor(x inv_cell) per axis, packed like cloud.pack_key."""
+    """float64 [M,3] -> (cell key int64 [M], ok bool [M]): cloud.grid_keys_numpy of x inv_cell.  ok: x is finite and in the key range
+    (an inf times inv_cell stays an inf and fails the range test); the key is INVALID_KEY where not ok and in the corner cell."""
     with np.errstate(invalid="ignore", over="ignore"):
-        f = np.floor(x * np.float64(ic))
-        ok = np.isfinite(x).all(1) & ((f >= -float(HALF)) & (f < float(HALF))).all(1)
-    c = np.where(ok[:, None], f, 0.0).astype(np.int64) + HALF
-    return (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2], ok
+        key, ok, _ = cloud.grid_keys_numpy((x * np.float64(ic)).T)
+    return key, ok
 
 
 def _xyz64(a, name):
@@ -171,8 +161,8 @@ def _xyz64(a, name):
 def grid_numpy(ref, tau):
     """ref float64 [M,3] -> Grid of numpy arrays."""
     x = _xyz64(ref, "ref")
-    key, ok = _cells_numpy(x, inv_cell(tau))
-    kept = np.nonzero(ok & (key != INVALID_KEY))[0]          # the one corner cell whose key is the sentinel holds nothing
+    key, _ = _cells_numpy(x, inv_cell(tau))
+    kept = np.nonzero(key != INVALID_KEY)[0]                 # the one corner cell whose key is the sentinel holds nothing
     order = kept[np.argsort(key[kept], kind="stable")]
     cell_key, starts, sizes = np.unique(key[order], return_index=True, return_counts=True)
     cell_start = np.concatenate([starts, [len(order)]]).astype(np.int64)
@@ -185,9 +175,30 @@ def _counts(d2, index, valid, thr2):
                     np.int64)
 
 
+def walk_numpy(grid, key):
+    """The walk of td_nn_query and td_cloud_normals (over csrc/td_grid.h's pieces) for all queries at once.  key int64 [n]: the cells of the valid queries -> yields (queries, rows):
+    indices into ``key`` and the rows of ``grid.points`` they visit, per (dx, dy) column (one lower and one upper bound over its at
+    most three z-cells) and per rank inside the column; every query at most once per yield."""
+    ix, iy, iz = cloud.unpack_key(key)
+    z0, z1 = np.maximum(iz - 1, -HALF), np.minimum(iz + 1, HALF - 1)
+    for dx in (-1, 0, 1):
+        for dy in (-1, 0, 1):
+            cx, cy = ix + dx, iy + dy
+            inside = (cx >= -HALF) & (cx < HALF) & (cy >= -HALF) & (cy < HALF)
+            cx, cy = np.where(inside, cx, 0), np.where(inside, cy, 0)
+            p0 = grid.cell_start[np.searchsorted(grid.cell_key, cloud._pack(cx, cy, z0), side="left")]
+            p1 = grid.cell_start[np.searchsorted(grid.cell_key, cloud._pack(cx, cy, z1), side="right")]
+            p1 = np.where(inside, p1, p0)
+            act, rank = np.nonzero(p1 > p0)[0], 0
+            while len(act):
+                yield act, p0[act] + rank
+                rank += 1
+                act = act[p0[act] + rank < p1[act]]
+
+
 def nearest_numpy(query, ref, tau, thresholds=None):
     """query float64 [N,3], ref float64 [M,3] (or a Grid of grid_numpy at the same tau) -> Neighbours.  The statement td_nn_query is
-    tested against: the same 9 columns of at most three cells, the candidates of a column visited rank by rank for all queries."""
+    tested against: walk_numpy's candidates."""
     q = _xyz64(query, "query")
     grid = ref if isinstance(ref, Grid) else grid_numpy(ref, tau)
     if grid.tau != float(tau):
@@ -199,26 +210,13 @@ def nearest_numpy(query, ref, tau, thresholds=None):
     best, best_index = np.full(N, np.inf), np.full(N, -1, np.int64)
     who = np.nonzero(valid)[0]
     if len(who) and len(grid.order):
-        ix, iy, iz = cloud.unpack_key(key[who])
-        z0, z1 = np.maximum(iz - 1, -HALF), np.minimum(iz + 1, HALF - 1)
-        for dx in (-1, 0, 1):
-            for dy in (-1, 0, 1):
-                cx, cy = ix + dx, iy + dy
-                inside = (cx >= -HALF) & (cx < HALF) & (cy >= -HALF) & (cy < HALF)
-                column = ((np.where(inside, cx, 0) + HALF) << 42) | ((np.where(inside, cy, 0) + HALF) << 21)
-                p0 = grid.cell_start[np.searchsorted(grid.cell_key, column | (z0 + HALF), side="left")]
-                p1 = grid.cell_start[np.searchsorted(grid.cell_key, column | (z1 + HALF), side="right")]
-                p1 = np.where(inside, p1, p0)
-                act, rank = np.nonzero(p1 > p0)[0], 0
-                while len(act):
-                    p, qi = p0[act] + rank, who[act]
-                    e = grid.points[p] - q[qi]
-                    d2 = ((e[:, 0] * e[:, 0]) + (e[:, 1] * e[:, 1])) + (e[:, 2] * e[:, 2])
-                    j = grid.order[p]
-                    take = (d2 <= tau2) & ((d2 < best[qi]) | ((d2 == best[qi]) & (j < best_index[qi])))
-                    best[qi[take]], best_index[qi[take]] = d2[take], j[take]
-                    rank += 1
-                    act = act[p0[act] + rank < p1[act]]
+        for act, p in walk_numpy(grid, key[who]):
+            qi = who[act]
+            e = grid.points[p] - q[qi]
+            d2 = ((e[:, 0] * e[:, 0]) + (e[:, 1] * e[:, 1])) + (e[:, 2] * e[:, 2])
+            j = grid.order[p]
+            take = (d2 <= tau2) & ((d2 < best[qi]) | ((d2 == best[qi]) & (j < best_index[qi])))
+            best[qi[take]], best_index[qi[take]] = d2[take], j[take]
     return Neighbours(best, best_index, _counts(best, best_index, valid, thr2))
 
 
@@ -325,9 +323,9 @@ def grid_hip(ref, tau):
                     {"points": 0, "dropped": 0, "cells": 0, "max_cell": 0})
     f = torch.floor(x * ic)
     ok = torch.isfinite(x).all(1) & ((f >= -float(HALF)) & (f < float(HALF))).all(1)
-    c = torch.where(ok[:, None], f, torch.zeros_like(f)).to(torch.int64) + HALF
-    key = (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2]
-    key = torch.where(ok, key, torch.full_like(key, INVALID_KEY))           # the corner cell's key is the sentinel already
+    c = torch.where(ok[:, None], f, torch.zeros_like(f)).to(torch.int64)
+    key = cloud._pack(c[:, 0], c[:, 1], c[:, 2])
+    key = torch.where(ok, key, torch.full_like(key, INVALID_KEY))         # the corner cell's key is the sentinel already
     sorted_keys, perm = torch.sort(key)
     heads = cloud.heads_hip(sorted_keys)
     starts = torch.nonzero(heads).reshape(-1)

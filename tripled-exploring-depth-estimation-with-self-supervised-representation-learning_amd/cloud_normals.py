@@ -61,7 +61,6 @@ import torch
 
 from . import cloud, cloud_eval, native
 
-HALF = cloud.HALF
 SWEEPS = 4                            # csrc/td_normals.hip: TD_NORMALS_SWEEPS
 QUANT = 2.0 ** 18                     # csrc/td_normals.hip: the host passes Q = QUANT / radius
 MAX_POINTS = 1 << 26                  # grid points: below it the integer sums cannot overflow
@@ -166,38 +165,24 @@ def _finish_numpy(sums, valid, min_neighbours, max_curvature):
 
 
 def _sums_numpy(q, grid, r2, Q):
-    """-> (sums int64 [N,10]: n, S1 (3), S2 (6);  valid bool [N]): the 9 columns of at most three cells, the candidates of a column
-    visited rank by rank for all queries."""
+    """-> (sums int64 [N,10]: n, S1 (3), S2 (6);  valid bool [N]) over cloud_eval.walk_numpy's candidates."""
     key, valid = cloud_eval._cells_numpy(q, cloud_eval.inv_cell(grid.tau))
     N = len(q)
     sums = np.zeros((N, 10), np.int64)
     who = np.nonzero(valid)[0]
     if len(who) and len(grid.points):
-        ix, iy, iz = cloud.unpack_key(key[who])
-        z0, z1 = np.maximum(iz - 1, -HALF), np.minimum(iz + 1, HALF - 1)
-        for dx in (-1, 0, 1):
-            for dy in (-1, 0, 1):
-                cx, cy = ix + dx, iy + dy
-                inside = (cx >= -HALF) & (cx < HALF) & (cy >= -HALF) & (cy < HALF)
-                column = ((np.where(inside, cx, 0) + HALF) << 42) | ((np.where(inside, cy, 0) + HALF) << 21)
-                p0 = grid.cell_start[np.searchsorted(grid.cell_key, column | (z0 + HALF), side="left")]
-                p1 = grid.cell_start[np.searchsorted(grid.cell_key, column | (z1 + HALF), side="right")]
-                p1 = np.where(inside, p1, p0)
-                act, rank = np.nonzero(p1 > p0)[0], 0
-                while len(act):
-                    qi = who[act]
-                    with np.errstate(invalid="ignore", over="ignore"):
-                        e = grid.points[p0[act] + rank] - q[qi]
-                        d2 = ((e[:, 0] * e[:, 0]) + (e[:, 1] * e[:, 1])) + (e[:, 2] * e[:, 2])
-                        take = d2 <= r2                                 # a NaN fails
-                        i = np.rint(e[take] * Q).astype(np.int64)
-                    rows = qi[take]                                     # every query at most once per rank: no repeated index
-                    sums[rows, 0] += 1
-                    sums[rows, 1:4] += i
-                    for at, (k, l) in enumerate(PAIRS):
-                        sums[rows, 4 + at] += i[:, k] * i[:, l]
-                    rank += 1
-                    act = act[p0[act] + rank < p1[act]]
+        for act, p in cloud_eval.walk_numpy(grid, key[who]):
+            qi = who[act]
+            with np.errstate(invalid="ignore", over="ignore"):
+                e = grid.points[p] - q[qi]
+                d2 = ((e[:, 0] * e[:, 0]) + (e[:, 1] * e[:, 1])) + (e[:, 2] * e[:, 2])
+                take = d2 <= r2                                 # a NaN fails
+                i = np.rint(e[take] * Q).astype(np.int64)
+            rows = qi[take]                                     # every query at most once per yield: no repeated index
+            sums[rows, 0] += 1
+            sums[rows, 1:4] += i
+            for at, (k, l) in enumerate(PAIRS):
+                sums[rows, 4 + at] += i[:, k] * i[:, l]
     return sums, valid
 
 

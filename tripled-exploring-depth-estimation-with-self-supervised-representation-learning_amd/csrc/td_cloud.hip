@@ -10,12 +10,10 @@
 // and sum of td_cloud_keys is rounded on its own, as the numpy statement (cloud.keys_numpy) rounds it.
 #include <math.h>
 
-#include "td_common.h"
+#include "td_grid.h"
 
 namespace td {
 
-#define TD_CLOUD_INVALID 0x7fffffffffffffffLL
-#define TD_CLOUD_HALF 1048576      // voxel coordinates lie in [-2^20, 2^20)
 #define TD_CLOUD_ITERS 8           // a wave's stretch of the sorted array: 8 x 64 elements
 #define TD_CLOUD_STRETCH (64 * TD_CLOUD_ITERS)
 
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_keys_kernel(const CloudKeyAr
     for (int j = 0; j < VEC; ++j) {
       const int x = x0 + j;
       int cause = 0;
-      long long kk = TD_CLOUD_INVALID;
+      long long kk = TD_KEY_INVALID;
       unsigned long long pp = 0;
       const double ds = (double)d[j] * a.depth_scale;
       if (x % a.stride != 0 || y % a.stride != 0) cause = 1;
@@ -127,29 +125,11 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_keys_kernel(const CloudKeyAr
         const double r1 = (a.ik[3] * u + a.ik[4] * v) + a.ik[5];
         const double r2 = (a.ik[6] * u + a.ik[7] * v) + a.ik[8];
         const double px = ds * r0, py = ds * r1, pz = ds * r2;
-        const double wx = ((P[0] * px + P[1] * py) + P[2] * pz) + a.pose_scale * P[3];
-        const double wy = ((P[4] * px + P[5] * py) + P[6] * pz) + a.pose_scale * P[7];
-        const double wz = ((P[8] * px + P[9] * py) + P[10] * pz) + a.pose_scale * P[11];
-        const double gx = wx * a.inv_voxel, gy = wy * a.inv_voxel, gz = wz * a.inv_voxel;
-        const double fx = floor(gx), fy = floor(gy), fz = floor(gz);
-        const double lo = -(double)TD_CLOUD_HALF, hi = (double)TD_CLOUD_HALF;
-        if (!(fx >= lo && fx < hi && fy >= lo && fy < hi && fz >= lo && fz < hi)) {      // a NaN fails every comparison
-          cause = 5;
-        } else {
-          const long long ix = (long long)fx + TD_CLOUD_HALF, iy = (long long)fy + TD_CLOUD_HALF,
-                          iz = (long long)fz + TD_CLOUD_HALF;
-          kk = (ix << 42) | (iy << 21) | iz;
-          if (kk == TD_CLOUD_INVALID) {      // the one corner voxel whose key is the sentinel
-            cause = 5;
-          } else {
-            int qx = (int)floor((gx - fx) * 1024.0), qy = (int)floor((gy - fy) * 1024.0), qz = (int)floor((gz - fz) * 1024.0);
-            qx = qx > 1023 ? 1023 : qx;
-            qy = qy > 1023 ? 1023 : qy;
-            qz = qz > 1023 ? 1023 : qz;
-            pp = (unsigned long long)qx | ((unsigned long long)qy << 10) | ((unsigned long long)qz << 20) |
-                 ((unsigned long long)cr[j] << 30) | ((unsigned long long)cg[j] << 38) | ((unsigned long long)cb[j] << 46);
-          }
-        }
+        double wx, wy, wz;
+        camera_to_world(P, a.pose_scale, px, py, pz, wx, wy, wz);
+        kk = voxel_key(wx * a.inv_voxel, wy * a.inv_voxel, wz * a.inv_voxel, pp);
+        if (kk == TD_KEY_INVALID) cause = 5;
+        else pp |= ((unsigned long long)cr[j] << 30) | ((unsigned long long)cg[j] << 38) | ((unsigned long long)cb[j] << 46);
       }
       key[j] = kk;
       pay[j] = pp;
@@ -175,7 +155,7 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_heads_kernel(const long long
   const long long i = (long long)blockIdx.x * TD_THREADS + threadIdx.x;
   if (i >= N) return;
   const long long k = keys[i];
-  flags[i] = (k != TD_CLOUD_INVALID && (i == 0 || keys[i - 1] != k)) ? 1 : 0;
+  flags[i] = (k != TD_KEY_INVALID && (i == 0 || keys[i - 1] != k)) ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -217,7 +197,7 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_reduce_kernel(const long lon
   const int lane = threadIdx.x & 63;
   const long long wave = (long long)blockIdx.x * (TD_THREADS / 64) + (threadIdx.x >> 6);
   const long long base = wave * TD_CLOUD_STRETCH;
-  if (base >= N || keys[base] == TD_CLOUD_INVALID) return;      // wave-uniform: invalid keys are sorted last
+  if (base >= N || keys[base] == TD_KEY_INVALID) return;      // wave-uniform: invalid keys are sorted last
   const long long end = base + TD_CLOUD_STRETCH < N ? base + TD_CLOUD_STRETCH : N;
   const long long first_s = seg[base];
   const bool first_open = base > 0 && seg[base - 1] == first_s;      // the first run began before this stretch
@@ -225,8 +205,8 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_reduce_kernel(const long lon
   long long carry_s = 0, carry[7] = {0, 0, 0, 0, 0, 0, 0};
   for (long long at = base; at < end; at += 64) {
     const long long idx = at + lane;
-    const long long k = idx < end ? keys[idx] : TD_CLOUD_INVALID;
-    const bool valid = k != TD_CLOUD_INVALID;
+    const long long k = idx < end ? keys[idx] : TD_KEY_INVALID;
+    const bool valid = k != TD_KEY_INVALID;
     const long long s = valid ? seg[idx] : -1;
     long long v[7] = {0, 0, 0, 0, 0, 0, 0};
     if (valid) {
@@ -278,7 +258,7 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_reduce_kernel(const long lon
     for (int j = 0; j < 7; ++j) carry[j] = __shfl(v[j], 63, 64);
   }
   if (carry_on) {
-    const bool closed = end >= N || keys[end] == TD_CLOUD_INVALID || seg[end] != carry_s;
+    const bool closed = end >= N || keys[end] == TD_KEY_INVALID || seg[end] != carry_s;
     const bool atomic = !closed || (carry_s == first_s && first_open);
     long long val = carry[0];
 #pragma unroll
@@ -303,8 +283,8 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_finish_kernel(const long lon
   const long long k = keys[i];
   const long long* s = sums + i * 7;
   const long long n = s[0];
-  const long long mask = 2 * TD_CLOUD_HALF - 1;
-  const long long c[3] = {((k >> 42) & mask) - TD_CLOUD_HALF, ((k >> 21) & mask) - TD_CLOUD_HALF, (k & mask) - TD_CLOUD_HALF};
+  const long long mask = 2 * TD_KEY_HALF - 1;
+  const long long c[3] = {((k >> TD_KEY_SHIFT_X) & mask) - TD_KEY_HALF, ((k >> TD_KEY_SHIFT_Y) & mask) - TD_KEY_HALF, (k & mask) - TD_KEY_HALF};
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     xyz[i * 3 + d] = (float)(((double)c[d] + ((double)s[1 + d] / (double)n + 0.5) / 1024.0) * voxel);

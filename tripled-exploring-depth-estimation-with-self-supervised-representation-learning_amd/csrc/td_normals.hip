@@ -1,6 +1,6 @@
 // Surface normals of a cloud (tripled_amd/cloud_normals.py):
 //   td_cloud_normals   one thread per query against a cloud that is sorted into td_nn_query's uniform grid of cells
-// The query walks the grid the way td_nn_query does (td_nn.hip: 9 lower bounds, at most three z-cells each) and gathers, over every
+// The query walks the grid the way td_nn_query does (td_nn.hip, over td_grid.h's pieces) and gathers, over every
 // grid point within `radius` of it, ten 64-bit INTEGER sums of the offsets quantised to radius 2^-18: the count, the three first and
 // the six second moments.  Integer sums do not depend on the order of the points inside a cell or on the order the cells are visited,
 // like the project's other exact kernels.  The covariance, its eigen-decomposition (cyclic Jacobi, a FIXED number of sweeps, only
@@ -10,11 +10,10 @@
 // 64-bit atomic per workgroup and counter.  Everything the Jacobi touches has a compile-time index: no scratch.
 #include <math.h>
 
-#include "td_common.h"
+#include "td_grid.h"
 
 namespace td {
 
-#define TD_NORMALS_HALF 1048576        // cell coordinates lie in [-2^20, 2^20): td_nn.hip's TD_NN_HALF
 #define TD_NORMALS_SWEEPS 4            // cloud_normals.SWEEPS
 #define TD_NORMALS_MAX_POINTS (1LL << 26)
 
@@ -31,19 +30,6 @@ struct NormalsArgs {
   long long* count;              // [N] (out)
   unsigned long long* counters;  // [5]: += valid, few, degenerate, rough, invalid
 };
-
-// the first c in [0, C] with cell_key[c] >= key; at most 64 halvings, every read inside [0, C)
-__device__ __forceinline__ long long normals_lower_bound(const long long* __restrict__ cell_key, long long C, long long key) {
-  long long lo = 0, hi = C;
-  for (int it = 0; it < 64 && lo < hi; ++it) {
-    const long long mid = lo + ((hi - lo) >> 1);
-    if (cell_key[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ long long normals_clamp(long long v, long long hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // One Jacobi rotation in the (p, q) plane of the symmetric matrix (app, aqq, apq; arp, arq: the third row's entries) and of the rows
 // of V (v0p, v0q, ...).  Skipped when apq is exactly 0.
@@ -80,28 +66,23 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_normals_kernel(const Normals
   const long long i = (long long)blockIdx.x * TD_THREADS + threadIdx.x;
   if (i < a.N) {
     const double qx = a.query[i * 3], qy = a.query[i * 3 + 1], qz = a.query[i * 3 + 2];
-    const double fx = floor(qx * a.inv_cell), fy = floor(qy * a.inv_cell), fz = floor(qz * a.inv_cell);
-    const double lo = -(double)TD_NORMALS_HALF, hi = (double)TD_NORMALS_HALF;
-    // a NaN or an inf fails a comparison
-    const bool valid = isfinite(qx) && isfinite(qy) && isfinite(qz) && fx >= lo && fx < hi && fy >= lo && fy < hi && fz >= lo && fz < hi;
+    long long ix, iy, iz;
+    const bool valid = grid_cell_of(qx, qy, qz, a.inv_cell, ix, iy, iz);
     long long n = 0, sx = 0, sy = 0, sz = 0, sxx = 0, sxy = 0, sxz = 0, syy = 0, syz = 0, szz = 0;
     if (valid) {
-      const long long ix = (long long)fx, iy = (long long)fy, iz = (long long)fz;
-      const long long z0 = iz - 1 < -TD_NORMALS_HALF ? -TD_NORMALS_HALF : iz - 1;
-      const long long z1 = iz + 1 > TD_NORMALS_HALF - 1 ? TD_NORMALS_HALF - 1 : iz + 1;
+      const long long z0 = iz - 1 < -TD_KEY_HALF ? -TD_KEY_HALF : iz - 1;
+      const long long z1 = iz + 1 > TD_KEY_HALF - 1 ? TD_KEY_HALF - 1 : iz + 1;
       for (int dx = -1; dx <= 1; ++dx) {
         const long long cx = ix + dx;
-        if (cx < -TD_NORMALS_HALF || cx >= TD_NORMALS_HALF) continue;
+        if (cx < -TD_KEY_HALF || cx >= TD_KEY_HALF) continue;
         for (int dy = -1; dy <= 1; ++dy) {
           const long long cy = iy + dy;
-          if (cy < -TD_NORMALS_HALF || cy >= TD_NORMALS_HALF) continue;
-          const long long column = ((cx + TD_NORMALS_HALF) << 42) | ((cy + TD_NORMALS_HALF) << 21);
-          const long long k0 = column | (z0 + TD_NORMALS_HALF), k1 = column | (z1 + TD_NORMALS_HALF);
-          const long long c0 = normals_lower_bound(a.cell_key, a.C, k0);
+          if (cy < -TD_KEY_HALF || cy >= TD_KEY_HALF) continue;
+          const long long c0 = grid_lower_bound(a.cell_key, a.C, key_pack(cx, cy, z0));
           long long c1 = c0;
-          while (c1 < a.C && c1 < c0 + 3 && a.cell_key[c1] <= k1) ++c1;      // at most the three z-neighbours
+          while (c1 < a.C && c1 < c0 + 3 && a.cell_key[c1] <= key_pack(cx, cy, z1)) ++c1;      // at most the three z-neighbours
           if (c1 == c0) continue;
-          const long long p0 = normals_clamp(a.cell_start[c0], a.M), p1 = normals_clamp(a.cell_start[c1], a.M);      // c1 <= C: inside [C+1]
+          const long long p0 = grid_row(a.cell_start[c0], a.M), p1 = grid_row(a.cell_start[c1], a.M);      // c1 <= C: inside [C+1]
           for (long long p = p0; p < p1; ++p) {
             const double ex = a.points[p * 3] - qx, ey = a.points[p * 3 + 1] - qy, ez = a.points[p * 3 + 2] - qz;
             const double d2 = ((ex * ex) + (ey * ey)) + (ez * ez);

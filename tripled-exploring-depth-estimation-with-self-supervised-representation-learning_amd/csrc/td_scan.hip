@@ -5,12 +5,9 @@
 // -ffp-contract=off: every float64 product and sum is rounded on its own, as the numpy statement (cloud_eval.scan_keys_numpy) rounds it.
 #include <math.h>
 
-#include "td_common.h"
+#include "td_grid.h"
 
 namespace td {
-
-#define TD_SCAN_INVALID 0x7fffffffffffffffLL
-#define TD_SCAN_HALF 1048576      // voxel coordinates lie in [-2^20, 2^20): td_cloud.hip's TD_CLOUD_HALF
 
 struct ScanKeyArgs {
   const float* points;         // [n,4] x, y, z, reflectance
@@ -58,7 +55,7 @@ __global__ __launch_bounds__(TD_THREADS) void scan_keys_kernel(const ScanKeyArgs
 #pragma unroll
       for (int j = 0; j < 4; ++j) p[j] = a.points[i * 4 + j];
     }
-    long long kk = TD_SCAN_INVALID;
+    long long kk = TD_KEY_INVALID;
     unsigned long long pp = 0;
     const int s = scan_of(a.offsets, a.S, i);
     cause = 0;
@@ -78,31 +75,16 @@ __global__ __launch_bounds__(TD_THREADS) void scan_keys_kernel(const ScanKeyArgs
           if (!(u >= 0.0 && u <= (double)(a.W - 1) && v >= 0.0 && v <= (double)(a.H - 1))) cause = 3;      // a NaN fails
         }
         if (cause == 0) {
-          const double* P = a.poses + (long long)s * 12;
-          const double wx = ((P[0] * cx + P[1] * cy) + P[2] * cz) + P[3];
-          const double wy = ((P[4] * cx + P[5] * cy) + P[6] * cz) + P[7];
-          const double wz = ((P[8] * cx + P[9] * cy) + P[10] * cz) + P[11];
-          const double gx = wx * a.inv_voxel, gy = wy * a.inv_voxel, gz = wz * a.inv_voxel;
-          const double fx = floor(gx), fy = floor(gy), fz = floor(gz);
-          const double lo = -(double)TD_SCAN_HALF, hi = (double)TD_SCAN_HALF;
-          if (!(fx >= lo && fx < hi && fy >= lo && fy < hi && fz >= lo && fz < hi)) {      // a NaN fails every comparison
+          double wx, wy, wz;
+          camera_to_world(a.poses + (long long)s * 12, 1.0, cx, cy, cz, wx, wy, wz);      // 1.0 t is t exactly
+          kk = voxel_key(wx * a.inv_voxel, wy * a.inv_voxel, wz * a.inv_voxel, pp);
+          if (kk == TD_KEY_INVALID) {
             cause = 4;
           } else {
-            const long long ix = (long long)fx + TD_SCAN_HALF, iy = (long long)fy + TD_SCAN_HALF, iz = (long long)fz + TD_SCAN_HALF;
-            kk = (ix << 42) | (iy << 21) | iz;
-            if (kk == TD_SCAN_INVALID) {      // the one corner voxel whose key is the sentinel
-              cause = 4;
-            } else {
-              int qx = (int)floor((gx - fx) * 1024.0), qy = (int)floor((gy - fy) * 1024.0), qz = (int)floor((gz - fz) * 1024.0);
-              qx = qx > 1023 ? 1023 : qx;
-              qy = qy > 1023 ? 1023 : qy;
-              qz = qz > 1023 ? 1023 : qz;
-              double c = floor((double)p[3] * 255.0 + 0.5);
-              c = c >= 0.0 ? (c <= 255.0 ? c : 255.0) : 0.0;      // a NaN reflectance is 0
-              const unsigned long long grey = (unsigned long long)c;
-              pp = (unsigned long long)qx | ((unsigned long long)qy << 10) | ((unsigned long long)qz << 20) | (grey << 30) |
-                   (grey << 38) | (grey << 46);
-            }
+            double c = floor((double)p[3] * 255.0 + 0.5);
+            c = c >= 0.0 ? (c <= 255.0 ? c : 255.0) : 0.0;      // a NaN reflectance is 0
+            const unsigned long long grey = (unsigned long long)c;
+            pp |= (grey << 30) | (grey << 38) | (grey << 46);
           }
         }
       }

@@ -7,11 +7,10 @@
 // with -ffp-contract=off and contains no fma: every float64 product, sum and quotient is rounded on its own, as numpy rounds it.
 #include <math.h>
 
-#include "td_common.h"
+#include "td_grid.h"
 
 namespace td {
 
-#define TD_VIEWS_INVALID 0x7fffffffffffffffLL      // td_cloud.hip: TD_CLOUD_INVALID
 #define TD_VIEWS_MAX_RADIUS 8
 #define TD_VIEWS_MAX_PLANE (1LL << 29)             // pixels of a frame: byte offsets inside it fit 32 bits
 
@@ -49,7 +48,7 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_views_kernel(const CloudView
   bool tested = false, dropped = false;
   if (pix < plane) {
     const long long out = (long long)ci * plane + pix;
-    tested = a.key ? a.key[out] != TD_VIEWS_INVALID : true;
+    tested = a.key ? a.key[out] != TD_KEY_INVALID : true;
     int n = 0;
     if (tested) {
       const float* __restrict__ centre = a.depth + (long long)i * plane;
@@ -62,10 +61,8 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_views_kernel(const CloudView
         const double r1 = (a.ik[3] * u + a.ik[4] * v) + a.ik[5];
         const double r2 = (a.ik[6] * u + a.ik[7] * v) + a.ik[8];
         const double px = ds * r0, py = ds * r1, pz = ds * r2;
-        const double* __restrict__ Pi = a.poses + (long long)i * 12;
-        const double wx = ((Pi[0] * px + Pi[1] * py) + Pi[2] * pz) + a.pose_scale * Pi[3];
-        const double wy = ((Pi[4] * px + Pi[5] * py) + Pi[6] * pz) + a.pose_scale * Pi[7];
-        const double wz = ((Pi[8] * px + Pi[9] * py) + Pi[10] * pz) + a.pose_scale * Pi[11];
+        double wx, wy, wz;
+        camera_to_world(a.poses + (long long)i * 12, a.pose_scale, px, py, pz, wx, wy, wz);
         int first = i - a.radius;                      // the window is shifted, not shortened, at the ends of [lo, hi)
         first = first < a.lo ? a.lo : first;
         first = first > a.hi - 1 - 2 * a.radius ? a.hi - 1 - 2 * a.radius : first;
@@ -103,7 +100,7 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_views_kernel(const CloudView
       if (n < a.min_views) {
         dropped = true;
         if (a.key) {
-          a.key[out] = TD_VIEWS_INVALID;
+          a.key[out] = TD_KEY_INVALID;
           a.payload[out] = 0ULL;
         }
       }
