@@ -8,7 +8,11 @@
  * The binding a maintainer of the reference would add is a ctypes stub: INTEGRATION.md.
  *
  * Conventions
- *   - every pointer is a DEVICE pointer unless the parameter comment says "host";
+ *   - every pointer is a DEVICE pointer unless the parameter is marked TD_HOST: an array the library reads on the host before it
+ *     launches (its values, or the device pointers it holds, travel in the kernel arguments).  The macro expands to nothing; the
+ *     ctypes binding reads it, and the numeric #defines below, from this file (tripled_amd/native.py: parse_header), so a
+ *     prototype here IS its Python signature: scalars are int / float / double / long long, a pointer to pointers is always
+ *     TD_HOST, a TD_HOST array of values has one of those four element types;
  *   - tensors are dense, NCHW, fp32, row-major (x fastest), exactly as the reference holds them -- except the colour
  *     frames of td_photo_fwd, which are RGBX pixels [B,H,W,4] produced from the reference's [B,3,H,W] tensors by
  *     td_photo_identity (as a by-product) or td_pack_rgbx (one 16-byte load per pixel or bilinear tap: the forward is bound
@@ -33,6 +37,7 @@ extern "C" {
 
 #define TD_ABI_VERSION 3      /* 3: fused bottleneck entry points (td_conv1x1_fwd_bnrelu, td_conv1x1_dgrad*, td_bn_*_partials); 2: td_photo_fwd takes RGBX frames (td_photo_identity emits them), idloss is [B,H,W,n_src], d_up has one plane per frame */
 #define TD_MAX_SRC 4
+#define TD_HOST               /* marks a parameter the library dereferences on the host (Conventions) */
 
 #define TD_OK 0
 #define TD_ERR_BAD_ARG (-1)      /* null pointer / non-positive size / n_src out of range */
@@ -68,8 +73,8 @@ int td_pack_rgbx(const float* img, int B, int H, int W, float* out, td_stream_t 
  *   tgt_rgbx, src_rgbx (out, both or neither NULL): [B,H,W,4] RGBX copies of the frames (x = 0), the frame format of
  *           td_photo_fwd -- written from the pixels this kernel reads anyway, which saves the td_pack_rgbx passes
  */
-int td_photo_identity(const float* tgt, const float* const* src, int n_src,
-                      int B, int H, int W, float* idloss, float* tgt_rgbx, float* const* src_rgbx, td_stream_t stream);
+int td_photo_identity(const float* tgt, TD_HOST const float* const* src, int n_src,
+                      int B, int H, int W, float* idloss, float* tgt_rgbx, TD_HOST float* const* src_rgbx, td_stream_t stream);
 
 /*
  * Fused per-scale photometric forward.  Replaces, for one scale,
@@ -98,7 +103,7 @@ int td_photo_identity(const float* tgt, const float* const* src, int n_src,
  *             (zeros where an identity term won), with  d SSIM_p / d x_q = (alpha + beta x_q + gamma y_q)/9
  *             for every member q of p's 3x3 window.
  */
-int td_photo_fwd(const float* tgt, const float* const* src, int n_src,
+int td_photo_fwd(const float* tgt, TD_HOST const float* const* src, int n_src,
                  const float* disp, const float* P, const float* invK,
                  const float* idloss, const float* noise,
                  int B, int H, int W, int hs, int ws,
@@ -118,7 +123,7 @@ int td_photo_fwd(const float* tgt, const float* const* src, int n_src,
  *             NCHW frames at the finest scale (2*hs >= H), where the disparity's detail breaks the coalescing of dword gathers
  * Follow with td_upsample_adjoint_planes (d_up planes -> d_disp) and td_reduce_dP.
  */
-int td_photo_bwd(const float* tgt, const float* const* src, const float* tgt_rgbx, const float* const* src_rgbx, int n_src,
+int td_photo_bwd(const float* tgt, TD_HOST const float* const* src, const float* tgt_rgbx, TD_HOST const float* const* src_rgbx, int n_src,
                  const float* disp, const float* P, const float* invK,
                  const uint8_t* argmin, const float* coef, int automask,
                  const float* gscale, float inv_count,
@@ -309,9 +314,10 @@ int td_conv1x1_wgrad(const void* dy, const void* x, long long M, int K, int N, i
  * dw[i], workspace[i]), bit for bit (same tiling / row ranges / summation order); all array arguments are HOST arrays of length n
  * (<= 4096).  A training step has ~90 independent 1x1 weight gradients that nothing needs before the optimiser step: enqueued by
  * the autograd nodes and launched together they stop being ~180 latency-bound launches (tripled_amd.ops.deferred_wgrads). */
-int td_conv1x1_wgrad_group(int n, const void* const* dy, const void* const* x, const long long* M, const int* K, const int* N,
-                           const int* Hi, const int* Wi, const int* stride, const int* dw_dtype, void* const* dw,
-                           float* const* workspace, td_stream_t stream);
+int td_conv1x1_wgrad_group(int n, TD_HOST const void* const* dy, TD_HOST const void* const* x, TD_HOST const long long* M,
+                           TD_HOST const int* K, TD_HOST const int* N, TD_HOST const int* Hi, TD_HOST const int* Wi,
+                           TD_HOST const int* stride, TD_HOST const int* dw_dtype, TD_HOST void* const* dw,
+                           TD_HOST float* const* workspace, td_stream_t stream);
 int td_bn_fwd_from_partials(const void* x, const void* residual, int dtype, const float* gamma, const float* beta,
                             float* running_mean, float* running_var, float momentum, float eps, int relu, long long M,
                             int groups, int C, float* partials, int stat_rows, void* y, float* save_mean,
@@ -349,8 +355,8 @@ int td_adam_flat(float* w, const float* grad, float* exp_avg, float* exp_avg_sq,
  * sources have the dtype src_dtype (bf16 or f32).  The gradient gather of the flat parameter store (tripled_amd/flat_amp.py):
  * replaces torch.cat over the per-parameter gradients + the bf16 -> f32 pass.
  */
-int td_gather_flat(const void* const* srcs, const long long* dst_offsets, const long long* numels, int n, int src_dtype, float* flat,
-                   td_stream_t stream);
+int td_gather_flat(TD_HOST const void* const* srcs, TD_HOST const long long* dst_offsets, TD_HOST const long long* numels, int n,
+                   int src_dtype, float* flat, td_stream_t stream);
 
 /*
  * Fused forms of the bottleneck's 1x1 convolutions (round 4): the BatchNorm passes of the NEIGHBOURING layers ride on the GEMM's
@@ -443,7 +449,7 @@ int td_bn_sync_bwd_dx(const void* dy, const void* x, const void* y, int dtype, c
  * td_featreg_bwd: grad = gscale[0] * d loss / d feat, same dtype/layout as feat.
  *   feat: [B,h,w,C] channels-last memory, C % 8 == 0, dtype TD_DTYPE_F32 or TD_DTYPE_BF16.
  */
-int td_edge_weights(const float* img, int B, int h, int w, float a, const float* scale6, float* Wt,
+int td_edge_weights(const float* img, int B, int h, int w, float a, TD_HOST const float* scale6, float* Wt,
                     td_stream_t stream);
 int td_featreg_num_blocks(int B, int h, int w, int C);
 int td_featreg_fwd(const void* feat, int dtype, const float* Wt, int B, int h, int w, int C,
@@ -500,13 +506,13 @@ int td_up2_reflpad1_bwd(const void* grad_out, int dtype, int N, int H, int W, in
  *   td_featwarp_num_blocks / B).
  */
 int td_featwarp_num_blocks(int B, int h, int w);
-int td_featwarp_fwd(const void* tgt, const void* const* src, int n_src, int dtype, const float* disp,
+int td_featwarp_fwd(const void* tgt, TD_HOST const void* const* src, int n_src, int dtype, const float* disp,
                     const float* P, const float* invK, int B, int h, int w, int C, int hs, int ws,
                     float min_depth, float max_depth, uint8_t* argmin, float* partial, td_stream_t stream);
-int td_featwarp_bwd(const void* tgt, const void* const* src, int n_src, int dtype, const float* disp,
+int td_featwarp_bwd(const void* tgt, TD_HOST const void* const* src, int n_src, int dtype, const float* disp,
                     const float* P, const float* invK, const uint8_t* argmin, const float* gscale,
                     float inv_count, int B, int h, int w, int C, int hs, int ws, float min_depth,
-                    float max_depth, void* d_tgt, int* const* d_src, float* d_up, float* dP_partial,
+                    float max_depth, void* d_tgt, TD_HOST int* const* d_src, float* d_up, float* dP_partial,
                     td_stream_t stream);
 /* out[i] = acc[i] * |gscale[0]| * inv_count / C / 2^14 (n elements, n % 8 == 0; dtype f32 or bf16): the scatter's accumulators
  * -> d/d(source features). */
@@ -528,9 +534,9 @@ int td_reduce_partials(const float* partial, int n_src, int B, int blocks_per_sa
  *   target        [B,C,H,W] fp32 NCHW;  out [B,1,H,W] fp32
  * td_l1map_bwd: dpred (same dtype and strides as pred) = gmap[b,y,x] * weight / C * (pred - target) / sqrt(...).
  */
-int td_l1map_fwd(const void* pred, int dtype, const long long* pred_strides, const float* target, int B, int C,
+int td_l1map_fwd(const void* pred, int dtype, TD_HOST const long long* pred_strides, const float* target, int B, int C,
                  int H, int W, float weight, float* out, td_stream_t stream);
-int td_l1map_bwd(const void* pred, int dtype, const long long* pred_strides, const float* target,
+int td_l1map_bwd(const void* pred, int dtype, TD_HOST const long long* pred_strides, const float* target,
                  const float* gmap, int B, int C, int H, int W, float weight, void* dpred, td_stream_t stream);
 
 /*
@@ -553,9 +559,9 @@ int td_rgb2lab(const float* rgb, int B, int H, int W, float l_cent, float l_norm
  *   T   [n_pairs,B,4,4] (out)     P  [n_pairs,B,3,4] = (K @ T)[:, :3, :] (out, may be NULL)
  * td_pose_bwd: g_axisangle / g_translation [n_pairs*B,3] from gT and/or gP (either may be NULL, not both).
  */
-int td_pose_fwd(const float* axisangle, const float* translation, const int* invert, const float* K,
+int td_pose_fwd(const float* axisangle, const float* translation, TD_HOST const int* invert, const float* K,
                 int n_pairs, int B, float* T, float* P, td_stream_t stream);
-int td_pose_bwd(const float* axisangle, const float* translation, const int* invert, const float* K,
+int td_pose_bwd(const float* axisangle, const float* translation, TD_HOST const int* invert, const float* K,
                 int n_pairs, int B, const float* gT, const float* gP, float* g_axisangle,
                 float* g_translation, td_stream_t stream);
 
@@ -684,12 +690,14 @@ int td_masked_median(const float* values, int B, long long n, void* workspace, l
  *        no frame lies more than len beyond first_frame (the row's errors and speed are then NaN)
  *   summary [2] float64 (out): c (1 without align_scale), total ground-truth distance
  */
+#define TD_ODOM_THREADS 256          /* the workgroup of td_odom_trajectory: a thread composes ceil(n / 256) transforms */
+#define TD_ODOM_MAX_LENGTHS 16       /* td_odom_sequence_errors: the most segment lengths of one call */
 int td_pose_pairs_u8(const uint8_t* frames, int n, int H, int W, int first, int count, int dtype, void* out, long long out_first,
                      td_stream_t stream);
 int td_odom_trajectory(const void* rel, int rel_f64, int n, double* poses, td_stream_t stream);
 int td_odom_snippet_ate(const void* rel, int rel_f64, const double* gt_poses, int n, int track_length, double* ates,
                         td_stream_t stream);
-int td_odom_sequence_errors(const double* gt_poses, const double* pred_poses, int m, const double* lengths, int n_lengths, int step,
+int td_odom_sequence_errors(const double* gt_poses, const double* pred_poses, int m, TD_HOST const double* lengths, int n_lengths, int step,
                             int align_scale, double* dist, double* rows, uint8_t* valid, double* summary, td_stream_t stream);
 
 /*
@@ -710,8 +718,9 @@ int td_odom_sequence_errors(const double* gt_poses, const double* pred_poses, in
  *   TD_ERR_BAD_ARG: n_sizes outside 1..16, a size larger than the canvas, offsets outside the buffer, a bad index in meta_host.
  *   TD_ERR_UNSUPPORTED: rows too wide for the LDS tile, N > 65535, a misaligned src.
  */
-int td_lanczos_resize_u8(const uint8_t* src, const int* meta, const int* meta_host, const int* tables, long long table_ints,
-                         const int* desc, int n_sizes, int N, int Hc, int Wc, int H, int W, uint8_t* dst, int* status,
+#define TD_RESIZE_MAX_SIZES 16       /* the most sizes of one bank (n_sizes, the rows of desc) */
+int td_lanczos_resize_u8(const uint8_t* src, const int* meta, TD_HOST const int* meta_host, const int* tables, long long table_ints,
+                         TD_HOST const int* desc, int n_sizes, int N, int Hc, int Wc, int H, int W, uint8_t* dst, int* status,
                          td_stream_t stream);
 
 /*
@@ -725,9 +734,10 @@ int td_lanczos_resize_u8(const uint8_t* src, const int* meta, const int* meta_ho
  *        the frame's own size when meta_host is given too, against the smallest size of the bank otherwise)
  *   TD_ERR_UNSUPPORTED: rows of the widest size too wide for the LDS tile, N > 65535, a misaligned store.
  */
-int td_lanczos_resize_u8_indexed(const uint8_t* store, long long store_bytes, const long long* offsets, const long long* offsets_host,
-                                 const int* meta, const int* meta_host, const int* tables, long long table_ints, const int* desc,
-                                 int n_sizes, int N, int H, int W, uint8_t* dst, int* status, td_stream_t stream);
+int td_lanczos_resize_u8_indexed(const uint8_t* store, long long store_bytes, const long long* offsets,
+                                 TD_HOST const long long* offsets_host, const int* meta, TD_HOST const int* meta_host, const int* tables,
+                                 long long table_ints, TD_HOST const int* desc, int n_sizes, int N, int H, int W, uint8_t* dst,
+                                 int* status, td_stream_t stream);
 
 /*
  * Fusion of depth maps and camera poses into a voxel-averaged coloured point cloud (csrc/td_cloud.hip, tripled_amd/cloud.py).
@@ -765,7 +775,7 @@ int td_lanczos_resize_u8_indexed(const uint8_t* store, long long store_bytes, co
  * td_cloud_finish.  keys [V], sums [V,7] -> xyz [V,3] float32 = (float)(((double)i + ((double)sum_q / (double)count + 0.5) / 1024.0)
  *   voxel);  rgb [V,3] uint8 = (2 sum_c + count) / (2 count), integer;  count [V] int32, saturating;  keep [V] uint8 = count >= min_count.
  */
-int td_cloud_keys(const float* depth, const uint8_t* color, const double* poses, const double* inv_K, int B, int H, int W,
+int td_cloud_keys(const float* depth, const uint8_t* color, const double* poses, TD_HOST const double* inv_K, int B, int H, int W,
                   double depth_scale, double pose_scale, double inv_voxel, int stride, int border, double min_depth, double max_range,
                   float edge, long long* key, unsigned long long* payload, long long* stats, td_stream_t stream);
 int td_cloud_heads(const long long* keys, long long N, int* flags, td_stream_t stream);
@@ -804,9 +814,11 @@ int td_cloud_finish(const long long* keys, const long long* sums, long long V, d
  *     c1 <= hi <= N, hi - lo < 2 radius + 1.  N = 0 or c0 = c1 is a successful no-op without a launch (checked before the window's
  *     length).  TD_ERR_UNSUPPORTED: a frame of more than 2^29 pixels (offsets inside a frame are 32-bit).
  */
-int td_cloud_views(const float* depth, const double* poses, const double* K, const double* inv_K, int N, int H, int W, int c0, int c1,
-                   int lo, int hi, int radius, int min_views, double tol, double depth_scale, double pose_scale, double min_depth,
-                   double max_range, long long* key, unsigned long long* payload, uint8_t* votes, long long* stats, td_stream_t stream);
+#define TD_VIEWS_MAX_RADIUS 8        /* the largest radius: 16 neighbouring frames */
+int td_cloud_views(const float* depth, const double* poses, TD_HOST const double* K, TD_HOST const double* inv_K, int N, int H, int W,
+                   int c0, int c1, int lo, int hi, int radius, int min_views, double tol, double depth_scale, double pose_scale,
+                   double min_depth, double max_range, long long* key, unsigned long long* payload, uint8_t* votes, long long* stats,
+                   td_stream_t stream);
 
 /*
  * KITTI ground-truth depth maps from velodyne scans, a batch of frames of different sizes per call (csrc/td_velo.hip,
@@ -870,8 +882,9 @@ int td_velo_depth(const float* points, const long long* offsets, int B, const do
  *   The table is a 64-bit integer minimum: no floating-point atomics, no kernel waits on another workgroup, two calls on the same
  *   inputs return the same bits.
  */
+#define TD_RENDER_MAX_SPLAT 8        /* the largest r: a splat covers at most 17 x 17 pixels */
 long long td_cloud_render_workspace_bytes(int C, int H, int W);
-int td_cloud_render(const float* xyz, const uint8_t* rgb, long long V, const double* poses, const double* K, int C, int H, int W,
+int td_cloud_render(const float* xyz, const uint8_t* rgb, long long V, const double* poses, TD_HOST const double* K, int C, int H, int W,
                     double pose_scale, double z_near, double z_far, double splat, int ortho, int bg_r, int bg_g, int bg_b,
                     void* workspace, long long workspace_bytes, float* depth, uint8_t* color, int* index, long long* stats,
                     td_stream_t stream);
@@ -922,11 +935,12 @@ int td_cloud_render(const float* xyz, const uint8_t* rgb, long long V, const dou
  *     with C > 0, thr2 null with K > 0, N < 0, M < 0, C < 0, C > M, K outside 0 .. 16, tau not > 0 or not finite.  N = 0 is a
  *     successful no-op without a launch;  M = 0 fills the "not found" answer.
  */
-int td_scan_keys(const float* points, long long n, const long long* offsets, int S, const double* Tr, const double* poses,
-                 const double* K, int H, int W, double min_depth, double max_range, double inv_voxel, long long* key,
+int td_scan_keys(const float* points, long long n, const long long* offsets, int S, TD_HOST const double* Tr, const double* poses,
+                 TD_HOST const double* K, int H, int W, double min_depth, double max_range, double inv_voxel, long long* key,
                  unsigned long long* payload, long long* stats, td_stream_t stream);
+#define TD_NN_MAX_THRESHOLDS 16      /* td_nn_query: the most thresholds (K) of one call */
 int td_nn_query(const double* query, long long N, const double* points, const long long* order, long long M, const long long* cell_key,
-                const long long* cell_start, long long C, double tau, const double* thr2, int K, double* d2, long long* index,
+                const long long* cell_start, long long C, double tau, TD_HOST const double* thr2, int K, double* d2, long long* index,
                 long long* counts, td_stream_t stream);
 
 /*
@@ -965,10 +979,12 @@ int td_nn_query(const double* query, long long N, const double* points, const lo
  *     that is not finite, workspace_bytes < 0, a workspace or out that is not 8-byte aligned; with N > 0: a null cur, index, d2 or
  *     workspace, ref null with M > 0.
  */
-int td_cloud_transform(const double* src, long long N, double c, const double* R, const double* t, double* out, td_stream_t stream);
+int td_cloud_transform(const double* src, long long N, double c, TD_HOST const double* R, TD_HOST const double* t, double* out,
+                       td_stream_t stream);
+#define TD_ICP_SLOTS 17              /* the sums of td_icp_moments: p (3), q (3), q_r p_c (9, row-major), |p|^2, d2 */
 long long td_icp_moments_workspace(long long N);
 int td_icp_moments(const double* cur, long long N, const double* ref, long long M, const long long* index, const double* d2, double trim2,
-                   const double* origin, void* workspace, long long workspace_bytes, double* out, td_stream_t stream);
+                   TD_HOST const double* origin, void* workspace, long long workspace_bytes, double* out, td_stream_t stream);
 
 /*
  * Point-to-plane alignment: surface normals of a cloud (csrc/td_normals.hip, tripled_amd/cloud_normals.py) and the sums of the
@@ -1013,13 +1029,15 @@ int td_icp_moments(const double* cur, long long N, const double* ref, long long 
  *     also for N = 0, which launches nothing else.
  *   TD_ERR_BAD_ARG before any launch: as td_icp_moments, and normals null with N > 0 and M > 0.
  */
+#define TD_NORMALS_SWEEPS 4          /* Jacobi sweeps of td_cloud_normals, never fewer */
 int td_cloud_normals(const double* query, long long N, const double* points, long long M, const long long* cell_key,
                      const long long* cell_start, long long C, double tau, double radius, double Q, long long min_neighbours,
                      double max_curvature, double* normal, double* curvature, long long* count, long long* counters, td_stream_t stream);
+#define TD_ICP_PLANE_SLOTS 37        /* the sums of td_icp_plane_moments: a_i a_j for i <= j, row-major (28), a_i r (7), r r, d2 */
 long long td_icp_plane_moments_workspace(long long N);
 int td_icp_plane_moments(const double* cur, long long N, const double* ref, const double* normals, long long M, const long long* index,
-                         const double* d2, double trim2, const double* origin, void* workspace, long long workspace_bytes, double* out,
-                         td_stream_t stream);
+                         const double* d2, double trim2, TD_HOST const double* origin, void* workspace, long long workspace_bytes,
+                         double* out, td_stream_t stream);
 
 /*
  * Surfel rendering (csrc/td_surfel.hip, tripled_amd/cloud_normals.py, tripled_amd/render.py): normals oriented towards the nearest
@@ -1065,8 +1083,10 @@ int td_icp_plane_moments(const double* cur, long long N, const double* ref, cons
  */
 int td_normals_orient(const float* xyz, const float* normal, long long V, const double* poses, int C, double pose_scale,
                       float* out_normal, int* camera, long long* stats, td_stream_t stream);
-int td_cloud_render_surfels(const float* xyz, const uint8_t* rgb, const float* normal, long long V, const double* poses, const double* K,
-                            int C, int H, int W, double pose_scale, double z_near, double z_far, double radius, int ortho, int cull,
+#define TD_SURFEL_MAX 16             /* the largest r: the pixel box of a disc is at most 33 x 33 */
+#define TD_SURFEL_SLACK 0.5009765625 /* 1/2 + 2^-10: 1/2 for rint(u) against u, 2^-10 for the rounding of the bound and of the pixel test */
+int td_cloud_render_surfels(const float* xyz, const uint8_t* rgb, const float* normal, long long V, const double* poses,
+                            TD_HOST const double* K, int C, int H, int W, double pose_scale, double z_near, double z_far, double radius, int ortho, int cull,
                             double ambient, int form, int bg_r, int bg_g, int bg_b, void* workspace, long long workspace_bytes,
                             float* depth, uint8_t* color, int* index, float* normal_map, long long* stats, td_stream_t stream);
 

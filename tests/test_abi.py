@@ -7,12 +7,39 @@ import re
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "tripled_hip.h")
 
 
 def _declared():
-    text = open(os.path.join(ROOT, "include", "tripled_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(td_[a-z_A-Z0-9]+)\s*\(", text)))
+    import tripled_amd  # noqa: F401
+    from tripled_amd import native
+    return sorted(native.parse_header(open(HEADER).read())[0])
+
+
+def test_argtypes_count_the_header_parameters():
+    """Per entry point: as many argtypes as the header's prototype has parameters (counted here from the text, commas and all, not by
+    the parser under test), and the last parameter is a td_stream_t exactly where native.call appends the stream: everywhere but
+    the queries (sizes, counts, error texts), which return something other than int or take only ints."""
+    import tripled_amd  # noqa: F401
+    from tripled_amd import native
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", open(HEADER).read(), flags=re.S)
+    protos = dict(re.findall(r"\b(td_\w+)\s*\(([^()]*)\)\s*;", text))
+    assert set(protos) == set(native.SIGNATURES) and len(protos) >= 115
+    launches = 0
+    for name, params in protos.items():
+        params = [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")]
+        restype, argtypes = native.SIGNATURES[name]
+        assert len(argtypes) == len(params), name
+        streamed = bool(params) and params[-1] == "td_stream_t stream"
+        assert sum(p.startswith("td_stream_t") for p in params) == streamed, name      # a stream is the last parameter or absent
+        if streamed:
+            launches += 1
+            assert restype is ctypes.c_int and argtypes[-1] is ctypes.c_void_p, name
+            assert native._plan(name)[0] == len(params) - 1
+        else:       # a query: native.call does not apply (it would take the last argument for the stream)
+            assert name.endswith(("_version", "_string", "_error", "_num_blocks", "_num_tasks", "_rows", "_floats", "_bytes",
+                                  "_workspace")), name
+    assert launches >= 90
 
 
 def test_header_symbols_exported():

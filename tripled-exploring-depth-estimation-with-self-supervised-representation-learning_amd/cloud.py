@@ -64,7 +64,7 @@ DEFAULT_MAX_RANGE = 1.0      # ~36 m: monocular depth degrades with range
 DEFAULT_EDGE = 0.1           # 10 % depth step to a 4-neighbour
 DEFAULT_VIEW_RADIUS = 2      # the multi-view filter (off by default: min_views = 0) asks the 2 frames before and the 2 after; UNTUNED
 DEFAULT_VIEW_TOL = 0.05      # 5 % of the smaller of the two depths; UNTUNED like the rest
-MAX_VIEW_RADIUS = 8          # csrc/td_views.hip: TD_VIEWS_MAX_RADIUS
+MAX_VIEW_RADIUS = native.CONSTANTS["TD_VIEWS_MAX_RADIUS"]
 
 Cloud = collections.namedtuple("Cloud", "xyz rgb count keys stats")
 Cloud.__doc__ = """xyz float32 [V,3], rgb uint8 [V,3], count int32 [V] (points fused into the voxel, saturating), keys int64 [V] (ascending:

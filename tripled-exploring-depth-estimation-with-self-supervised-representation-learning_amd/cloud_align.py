@@ -58,10 +58,10 @@ import torch
 
 from . import cloud_eval, cloud_normals, native
 
-SLOTS = 17                            # csrc/td_align.hip: TD_ICP_SLOTS
+SLOTS = native.CONSTANTS["TD_ICP_SLOTS"]
 BLOCK = 256                           # rows per workgroup of stage 1, threads of stage 2
 MODES = ("similarity", "rigid")
-PLANE_SLOTS = 37                      # csrc/td_align.hip: TD_ICP_PLANE_SLOTS
+PLANE_SLOTS = native.CONSTANTS["TD_ICP_PLANE_SLOTS"]
 CRITERIA = ("point", "plane")
 
 Alignment = collections.namedtuple("Alignment", "scale R t iterations converged history")

@@ -40,7 +40,7 @@ from . import cloud, infer, native
 HALF = cloud.HALF
 INVALID_KEY = cloud.INVALID_KEY
 SCAN_CAUSES = ("valid", "invalid_point", "invalid_depth", "invalid_view", "invalid_range")
-MAX_THRESHOLDS = 16                   # csrc/td_nn.hip: TD_NN_MAX_THRESHOLDS
+MAX_THRESHOLDS = native.CONSTANTS["TD_NN_MAX_THRESHOLDS"]
 
 # UNTUNED, like cloud.DEFAULT_VOXEL it is derived from: three voxels, in the clouds' units.  Nobody has scored a real cloud with it.
 DEFAULT_TAU = 3 * cloud.DEFAULT_VOXEL

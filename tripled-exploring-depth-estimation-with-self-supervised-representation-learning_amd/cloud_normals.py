@@ -61,7 +61,7 @@ import torch
 
 from . import cloud, cloud_eval, native
 
-SWEEPS = 4                            # csrc/td_normals.hip: TD_NORMALS_SWEEPS
+SWEEPS = native.CONSTANTS["TD_NORMALS_SWEEPS"]
 QUANT = 2.0 ** 18                     # csrc/td_normals.hip: the host passes Q = QUANT / radius
 MAX_POINTS = 1 << 26                  # grid points: below it the integer sums cannot overflow
 CAUSES = ("valid", "few", "degenerate", "rough", "invalid")

@@ -15,8 +15,6 @@
 
 namespace td {
 
-#define TD_ICP_SLOTS 17      // p (3), q (3), q_r p_c (9, row-major), |p|^2, d2
-
 struct TransformArgs {
   const double* src;      // [N,3]
   double* out;            // [N,3] (may be src)
@@ -111,7 +109,6 @@ __global__ __launch_bounds__(TD_THREADS) void icp_moments_finish_kernel(const Mo
 }
 
 // ---- point to plane ------------------------------------------------------------------------------------------------------------------
-#define TD_ICP_PLANE_SLOTS 37      // a_i a_j for i <= j, row-major (28), a_i r (7), r r, d2
 #define TD_ICP_PLANE_GROUP 13      // slots per trip through the LDS tree: 37 = 13 + 13 + 11
 
 struct PlaneMomentsArgs {

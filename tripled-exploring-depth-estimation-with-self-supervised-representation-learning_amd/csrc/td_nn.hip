@@ -12,8 +12,6 @@
 
 namespace td {
 
-#define TD_NN_MAX_THRESHOLDS 16
-
 struct NnArgs {
   const double* query;           // [N,3]
   const double* points;          // [M',3] the reference, in cell order

@@ -14,7 +14,6 @@
 
 namespace td {
 
-#define TD_NORMALS_SWEEPS 4            // cloud_normals.SWEEPS
 #define TD_NORMALS_MAX_POINTS (1LL << 26)
 
 struct NormalsArgs {

@@ -14,9 +14,6 @@
 
 namespace td {
 
-#define TD_ODOM_THREADS 256
-#define TD_ODOM_MAX_LENGTHS 16
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // pairs
 

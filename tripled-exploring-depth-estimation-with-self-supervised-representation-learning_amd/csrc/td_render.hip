@@ -16,7 +16,6 @@
 namespace td {
 
 #define TD_RENDER_NONE 0xffffffffffffffffULL
-#define TD_RENDER_MAX_SPLAT 8
 
 struct RenderArgs {
   const float* xyz;                // [V,3]

@@ -29,8 +29,6 @@
 #include <algorithm>
 #include <climits>
 
-#define TD_RESIZE_MAX_SIZES 16
-
 namespace td {
 
 struct ResizeDesc { int h, w, ksx, ksy, off_kx, off_bx, off_ky, off_by; };

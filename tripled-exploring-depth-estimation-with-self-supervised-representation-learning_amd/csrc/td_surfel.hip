@@ -19,9 +19,7 @@
 namespace td {
 
 #define TD_SURFEL_NONE 0xffffffffffffffffULL
-#define TD_SURFEL_MAX 16               // render.MAX_SURFEL: the largest box is 33 x 33
 #define TD_SURFEL_OWN 4                // a box of at most this many pixels is drawn by its own thread (form 2); measured: DESIGN 27
-#define TD_SURFEL_SLACK 0.5009765625   // 1/2 for rint(u) against u, 2^-10 for the rounding of the bound and of the pixel test
 #define TD_ORIENT_CHUNK 256
 
 // ---------------------------------------------------------------------------------------------------------------------------

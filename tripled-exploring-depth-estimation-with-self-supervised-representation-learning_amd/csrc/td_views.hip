@@ -11,7 +11,6 @@
 
 namespace td {
 
-#define TD_VIEWS_MAX_RADIUS 8
 #define TD_VIEWS_MAX_PLANE (1LL << 29)             // pixels of a frame: byte offsets inside it fit 32 bits
 
 struct CloudViewArgs {

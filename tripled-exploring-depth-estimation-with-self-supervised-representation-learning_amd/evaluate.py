@@ -24,7 +24,7 @@ METRICS = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 COLUMNS = METRICS + ("scale",)
 MIN_DEPTH = 1e-3
 MAX_DEPTH = 80
-STEREO_SCALE_FACTOR = 36          # include/tripled_hip.h: TD_STEREO_SCALE_FACTOR
+STEREO_SCALE_FACTOR = native.CONSTANTS["TD_STEREO_SCALE_FACTOR"]
 
 
 def garg_crop(gt_h, gt_w):

@@ -4,7 +4,9 @@ There is deliberately no fallback: if the shared library is missing or a call re
 error code, an exception is raised.  Nothing in here touches ``oracle/``.
 """
 import ctypes
+import functools
 import os
+import re
 
 import torch
 
@@ -12,153 +14,90 @@ from . import dispatch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libtripled_hip.so")
-
-TD_MAX_SRC = 4
-
-# name -> (restype, argtypes); mirrors include/tripled_hip.h one to one
-_PTRARR = ctypes.POINTER(ctypes.c_void_p)
-_I, _F, _P = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
-_LLARR = ctypes.POINTER(ctypes.c_longlong)     # host arrays
-_IARR = ctypes.POINTER(ctypes.c_int)
-ABI_VERSION = 3      # include/tripled_hip.h: TD_ABI_VERSION
-
-SIGNATURES = {
-    "td_abi_version": (_I, []),
-    "td_error_string": (ctypes.c_char_p, [_I]),
-    "td_last_hip_error": (ctypes.c_char_p, []),
-    "td_photo_num_blocks": (_I, [_I, _I, _I]),
-    "td_photo_bwd_num_blocks": (_I, [_I, _I, _I]),
-    "td_photo_identity": (_I, [_P, _PTRARR, _I, _I, _I, _I, _P, _P, _PTRARR, _P]),
-    "td_photo_fwd": (_I, [_P, _PTRARR, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
-    "td_photo_bwd": (_I, [_P, _PTRARR, _P, _PTRARR, _I, _P, _P, _P, _P, _P, _I, _P, _F, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
-    "td_pack_rgbx": (_I, [_P, _I, _I, _I, _P, _P]),
-    "td_upsample_adjoint": (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P]),
-    "td_upsample_adjoint_planes": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
-    "td_reduce_dP": (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    "td_sum_scaled": (_I, [_P, _I, _F, _P, _P]),
-    "td_area_downsample": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "td_smooth_num_blocks": (_I, [_I, _I, _I]),
-    "td_smooth_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    "td_smooth_finish": (_I, [_P, _I, _I, _I, _F, _P, _P]),
-    "td_smooth_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _I, _P]),
-    "td_maxpool5_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "td_maxpool5_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "td_maxpool5_bwd_add": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "td_conv1x1_fwd_sum": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _P, _P, _P, _P]),
-    "td_maxpool3s2_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "td_maxpool3s2_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "td_join_fwd": (_I, [_P, _P, _P, _I, ctypes.c_longlong, _I, _I, _I, _P, _P]),
-    "td_join_bwd": (_I, [_P, _I, ctypes.c_longlong, _I, _I, _I, _P, _P, _P, _P]),
-    "td_join_up2_fwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "td_join_up2_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "td_bn_workspace_floats": (ctypes.c_longlong, [ctypes.c_longlong, _I, _I]),
-    "td_bn_fwd": (_I, [_P, _P, _I, _P, _P, _P, _P, _F, _F, _I, ctypes.c_longlong, _I, _I, _P, _P, _P, _P, _P]),
-    "td_conv1x1_stat_rows": (_I, [ctypes.c_longlong, _I, _I]),
-    "td_conv1x1_fwd": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "td_conv3x3_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "td_conv3x3_wgrad_workspace_floats": (ctypes.c_longlong, [_I, _I, _I, _I, _I]),
-    "td_conv3x3_wgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "td_conv1x1_wgrad_workspace_floats": (ctypes.c_longlong, [ctypes.c_longlong, _I, _I]),
-    "td_conv1x1_wgrad": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "td_conv1x1_wgrad_group": (_I, [_I, _PTRARR, _PTRARR, _LLARR, _IARR, _IARR, _IARR, _IARR, _IARR, _IARR, _PTRARR, _PTRARR, _P]),
-    "td_bn_fwd_from_partials": (_I, [_P, _P, _I, _P, _P, _P, _P, _F, _F, _I, ctypes.c_longlong, _I, _I, _P, _I, _P, _P, _P, _P]),
-    "td_bias_act_workspace_floats": (ctypes.c_longlong, [ctypes.c_longlong, _I]),
-    "td_bias_act_fwd": (_I, [_P, _P, _I, _I, ctypes.c_longlong, _I, _I, _P, _P]),
-    "td_bias_act_bwd": (_I, [_P, _P, _I, ctypes.c_longlong, _I, _I, _P, _P, _I, _P, _P]),
-    "td_gather_flat": (_I, [_PTRARR, _LLARR, _LLARR, _I, _I, _P, _P]),
-    "td_adam_flat": (_I, [_P, _P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _F, ctypes.c_double, ctypes.c_double, _F, _P, _F, _P]),
-    "td_bn_partial_rows": (_I, [ctypes.c_longlong, _I, _I]),
-    "td_bn_fwd_partials": (_I, [_P, _I, ctypes.c_longlong, _I, _I, _P, _P]),
-    "td_bn_bwd_partials": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, ctypes.c_longlong, _I, _I, _P, _P]),
-    "td_bn_bwd_from_partials": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, ctypes.c_longlong, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
-    "td_conv1x1_fwd_bnrelu": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _I, _P, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P]),
-    "td_conv1x1_dgrad": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _I, _P, _P, _P]),
-    "td_conv1x1_dgrad_bnsums": (_I, [_P, _P, ctypes.c_longlong, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "td_conv1x1_dgrad_bnbwd": (_I, [_P, _P, _P, ctypes.c_longlong, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "td_bn_bwd": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, ctypes.c_longlong, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "td_edge_weights": (_I, [_P, _I, _I, _I, _F, ctypes.POINTER(ctypes.c_float), _P, _P]),
-    "td_featreg_num_blocks": (_I, [_I, _I, _I, _I]),
-    "td_featreg_fwd": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P]),
-    "td_featreg_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
-    "td_recon_num_tasks": (_I, [_I, _I, _I]),
-    "td_recon_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
-    "td_recon_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
-    "td_reflpad1_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    "td_reflpad1_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    "td_up2_reflpad1_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    "td_up2_reflpad1_bwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    "td_featwarp_num_blocks": (_I, [_I, _I, _I]),
-    "td_featwarp_fwd": (_I, [_P, _PTRARR, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P, _P, _P]),
-    "td_featwarp_bwd": (_I, [_P, _PTRARR, _I, _I, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _F, _F, _P, _PTRARR,
-                             _P, _P, _P]),
-    "td_featwarp_dsrc_finish": (_I, [_P, _P, _F, _I, ctypes.c_longlong, _I, _P, _P]),
-    "td_reduce_partials": (_I, [_P, _I, _I, _I, _P, _P]),
-    "td_bn_sync_fwd_sums": (_I, [_P, _I, ctypes.c_longlong, _I, _I, _P, _P, _P]),
-    "td_bn_sync_fwd_apply": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _F, _F, _I, ctypes.c_longlong, _I, _I, _P, _P, _P, _P]),
-    "td_bn_sync_bwd_sums": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, ctypes.c_longlong, _I, _I, _P, _P, _P]),
-    "td_bn_sync_bwd_dx": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, ctypes.c_longlong, _I, _I, _P, _P, _P, _P, _P, _P]),
-    "td_fp8_num_blocks": (_I, [ctypes.c_longlong]),
-    "td_fp8_amax_partials": (_I, [_P, _I, ctypes.c_longlong, _P, _P]),
-    "td_fp8_quantize": (_I, [_P, _I, ctypes.c_longlong, _P, _P, _P, _P]),
-    "td_color_jitter": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    "td_l1map_fwd": (_I, [_P, _I, _LLARR, _P, _I, _I, _I, _I, _F, _P, _P]),
-    "td_l1map_bwd": (_I, [_P, _I, _LLARR, _P, _P, _I, _I, _I, _I, _F, _P, _P]),
-    "td_rgb2lab": (_I, [_P, _I, _I, _I, _F, _F, _F, _P, _P]),
-    "td_pose_fwd": (_I, [_P, _P, _IARR, _P, _I, _I, _P, _P, _P]),
-    "td_pose_bwd": (_I, [_P, _P, _IARR, _P, _I, _I, _P, _P, _P, _P, _P]),
-    "td_infer_preprocess": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "td_disp_postprocess": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _F, _F, _F, _P, _P, _P]),
-    "td_colorize": (_I, [_P, _I, ctypes.c_longlong, _P, _P, _P, _P, _P]),
-    "td_eval_depth_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
-    "td_eval_depth": (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _I, _I, _P, _P, _F, _F, _I, _P, ctypes.c_longlong, _P, _P, _P]),
-    "td_masked_median_workspace_bytes": (ctypes.c_longlong, [_I]),
-    "td_masked_median": (_I, [_P, _I, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, _P]),
-    "td_pose_pairs_u8": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, ctypes.c_longlong, _P]),
-    "td_odom_trajectory": (_I, [_P, _I, _I, _P, _P]),
-    "td_odom_snippet_ate": (_I, [_P, _I, _P, _I, _I, _P, _P]),
-    "td_odom_sequence_errors": (_I, [_P, _P, _I, ctypes.POINTER(ctypes.c_double), _I, _I, _I, _P, _P, _P, _P, _P]),
-    "td_lanczos_resize_u8": (_I, [_P, _P, _IARR, _P, ctypes.c_longlong, _IARR, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "td_lanczos_resize_u8_indexed": (_I, [_P, ctypes.c_longlong, _P, _LLARR, _P, _IARR, _P, ctypes.c_longlong, _IARR, _I, _I, _I, _I, _P,
-                                          _P, _P]),
-    "td_cloud_keys": (_I, [_P, _P, _P, ctypes.POINTER(ctypes.c_double), _I, _I, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                           _I, _I, ctypes.c_double, ctypes.c_double, _F, _P, _P, _P, _P]),
-    "td_cloud_heads": (_I, [_P, ctypes.c_longlong, _P, _P]),
-    "td_cloud_reduce_packed": (_I, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
-    "td_cloud_reduce_rows": (_I, [_P, _P, _P, _P, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, _P, _P, _P]),
-    "td_cloud_finish": (_I, [_P, _P, ctypes.c_longlong, ctypes.c_double, ctypes.c_longlong, _P, _P, _P, _P, _P]),
-    "td_cloud_views": (_I, [_P, _P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), _I, _I, _I, _I, _I, _I, _I, _I, _I,
-                            ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P, _P]),
-    "td_velo_depth_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
-    "td_velo_depth": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P]),
-    "td_cloud_render_workspace_bytes": (ctypes.c_longlong, [_I, _I, _I]),
-    "td_cloud_render": (_I, [_P, _P, ctypes.c_longlong, _P, ctypes.POINTER(ctypes.c_double), _I, _I, _I, ctypes.c_double, ctypes.c_double,
-                             ctypes.c_double, ctypes.c_double, _I, _I, _I, _I, _P, ctypes.c_longlong, _P, _P, _P, _P, _P]),
-    "td_scan_keys": (_I, [_P, ctypes.c_longlong, _P, _I, ctypes.POINTER(ctypes.c_double), _P, ctypes.POINTER(ctypes.c_double), _I, _I,
-                          ctypes.c_double, ctypes.c_double, ctypes.c_double, _P, _P, _P, _P]),
-    "td_nn_query": (_I, [_P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, ctypes.c_double,
-                         ctypes.POINTER(ctypes.c_double), _I, _P, _P, _P, _P]),
-    "td_cloud_transform": (_I, [_P, ctypes.c_longlong, ctypes.c_double, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                                _P, _P]),
-    "td_icp_moments_workspace": (ctypes.c_longlong, [ctypes.c_longlong]),
-    "td_icp_moments": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, ctypes.c_double, ctypes.POINTER(ctypes.c_double), _P,
-                            ctypes.c_longlong, _P, _P]),
-    "td_cloud_normals": (_I, [_P, ctypes.c_longlong, _P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, ctypes.c_double, ctypes.c_double,
-                              ctypes.c_double, ctypes.c_longlong, ctypes.c_double, _P, _P, _P, _P, _P]),
-    "td_icp_plane_moments_workspace": (ctypes.c_longlong, [ctypes.c_longlong]),
-    "td_icp_plane_moments": (_I, [_P, ctypes.c_longlong, _P, _P, ctypes.c_longlong, _P, _P, ctypes.c_double,
-                                  ctypes.POINTER(ctypes.c_double), _P, ctypes.c_longlong, _P, _P]),
-    "td_normals_orient": (_I, [_P, _P, ctypes.c_longlong, _P, _I, ctypes.c_double, _P, _P, _P, _P]),
-    "td_cloud_render_surfels": (_I, [_P, _P, _P, ctypes.c_longlong, _P, ctypes.POINTER(ctypes.c_double), _I, _I, _I, ctypes.c_double,
-                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _I, _I, ctypes.c_double, _I, _I, _I, _I, _P,
-                                     ctypes.c_longlong, _P, _P, _P, _P, _P, _P]),
-}
-
-DTYPE_CODES = {torch.float32: 0, torch.bfloat16: 1}
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tripled_hip.h")
 
 
 class NativeLibraryError(RuntimeError):
     pass
 
+
+_I, _P = ctypes.c_int, ctypes.c_void_p
+_PTRARR = ctypes.POINTER(ctypes.c_void_p)      # a TD_HOST array of device pointers
+_SCALARS = {"int": _I, "float": ctypes.c_float, "double": ctypes.c_double, "long long": ctypes.c_longlong}
+_RETURNS = {"int": _I, "long long": ctypes.c_longlong, "const char*": ctypes.c_char_p}
+
+
+@functools.lru_cache(maxsize=None)
+def _slot(ctype):
+    """The ctypes type of a parameter type of the header (the closed map of parse_header); None for anything outside it."""
+    words = ctype.replace("*", " * ").split()
+    host, stars = words[:1] == ["TD_HOST"], words.count("*")
+    base = " ".join(w for w in words[host:] if w not in ("const", "*"))
+    if not base:
+        return None
+    if host:      # a typed host array, or a host array of device pointers
+        return _PTRARR if stars == 2 else ctypes.POINTER(_SCALARS[base]) if stars == 1 and base in _SCALARS else None
+    if stars == 0:
+        return _P if base == "td_stream_t" else _SCALARS.get(base)
+    return _P if stars == 1 else None      # a device pointer or an opaque workspace, whatever it points to; never a T**
+
+
+def parse_header(text):
+    """include/tripled_hip.h -> ({entry point: (restype, argtypes)}, {TD_NAME: number}): the ONE statement of the C ABI, read, not
+    restated.  Not a C parser: it knows the few forms the header uses and raises ValueError on anything else, so a prototype it
+    cannot read is never a missing entry.  Constants: ``#define TD_NAME literal`` (an integer, bare or in parentheses, or a decimal
+    floating literal; a define without a value is ignored).  Types: int / float / double / long long scalars, td_stream_t and any
+    unmarked ``T*`` -> c_void_p (a device pointer), ``TD_HOST T* const*`` -> POINTER(c_void_p), ``TD_HOST const T*`` with T one of
+    the four scalars -> POINTER(c_T); an unmarked ``T**`` is an error (there are no device arrays of pointers).  Returns int,
+    long long or const char*.  Parameters are written ``type name``, the stars with the type."""
+    text = re.sub(r"/\*[^*]*\*+(?:[^/*][^*]*\*+)*/|//[^\n]*", " ", text)      # comments (the unrolled form of /\*.*?\*/: 5x faster)
+    constants = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(TD_\w+)[ \t]+(\S.*?)[ \t]*$", text, re.M):
+        m = re.fullmatch(r"\(\s*(-?\d+)\s*\)|(-?\d+)|(-?\d+\.\d+)", value)
+        if not m:
+            raise ValueError("#define %s %s: the value is not an integer or decimal literal" % (name, value))
+        constants[name] = float(m.group(3)) if m.group(3) else int(m.group(1) or m.group(2))
+    # the lines of the preprocessor, of the extern "C" braces and of typedefs go; what is left is prototypes, each closed by its ';'
+    text = re.sub(r'^[ \t]*(?:#.*|\}|extern[ \t]+"C"[ \t]*\{|typedef\b[^;\n]*;)[ \t]*$', "", text, flags=re.M)
+    *declarations, rest = " ".join(text.split()).split(";")
+    if rest:
+        raise ValueError("not a prototype (no terminating ';'): %r" % rest)
+    signatures = {}
+    for decl in declarations:
+        m = re.fullmatch(r" ?(.*?) ?\b(\w+) ?\(([^()]*)\) ?", decl)
+        ret = m and m.group(1).replace(" *", "*")
+        if not m or ret not in _RETURNS or m.group(2) in signatures:
+            raise ValueError("not a prototype this binding can read: %r" % decl.strip())
+        name, params = m.group(2), m.group(3).strip()
+        if not params:
+            raise ValueError("%s: an empty parameter list; write (void)" % name)
+        argtypes = []
+        for param in [] if params == "void" else params.split(","):
+            ctype, _, pname = param.strip().rpartition(" ")
+            slot = _slot(ctype) if pname.isidentifier() else None
+            if slot is None:
+                raise ValueError("%s: parameter %r is outside the types this binding reads (int, float, double, long long, "
+                                 "td_stream_t, T*, TD_HOST T* const*, TD_HOST const int / long long / float / double*)"
+                                 % (name, param.strip()))
+            argtypes.append(slot)
+        signatures[name] = (_RETURNS[ret], argtypes)
+    return signatures, constants
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise NativeLibraryError("include/tripled_hip.h not found at %s (%s) -- the ctypes signatures and the limits of the "
+                                 "bindings are derived from it; there is no restated copy" % (HEADER_PATH, e)) from e
+
+
+# name -> (restype, argtypes), and the header's numeric #defines: derived once per process, never written down here
+SIGNATURES, CONSTANTS = parse_header(_read_header())
+ABI_VERSION = CONSTANTS["TD_ABI_VERSION"]
+TD_MAX_SRC = CONSTANTS["TD_MAX_SRC"]
+DTYPE_CODES = {torch.float32: CONSTANTS["TD_DTYPE_F32"], torch.bfloat16: CONSTANTS["TD_DTYPE_BF16"]}
 
 _lib = None
 

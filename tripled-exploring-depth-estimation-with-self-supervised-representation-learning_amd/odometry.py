@@ -30,8 +30,8 @@ from . import infer, native
 LENGTHS = (100, 200, 300, 400, 500, 600, 700, 800)
 STEP = 10
 TRACK_LENGTH = 5
-MAX_LENGTHS = 16         # csrc/td_odom.hip: TD_ODOM_MAX_LENGTHS
-TRAJECTORY_THREADS = 256  # csrc/td_odom.hip: TD_ODOM_THREADS, the workgroup of td_odom_trajectory (a thread owns ceil(n / 256) steps)
+MAX_LENGTHS = native.CONSTANTS["TD_ODOM_MAX_LENGTHS"]
+TRAJECTORY_THREADS = native.CONSTANTS["TD_ODOM_THREADS"]      # the workgroup of td_odom_trajectory (a thread owns ceil(n / 256) steps)
 
 OdometryResult = collections.namedtuple(
     "OdometryResult", "ate_mean ate_std t_err r_err scale distance poses ates segments relative")

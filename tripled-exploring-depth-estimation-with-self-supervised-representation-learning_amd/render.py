@@ -65,7 +65,7 @@ import torch
 
 from . import cloud, native
 
-MAX_SPLAT = 8                        # csrc/td_render.hip: TD_RENDER_MAX_SPLAT
+MAX_SPLAT = native.CONSTANTS["TD_RENDER_MAX_SPLAT"]
 STATS = ("points", "out_of_range", "outside", "drawn", "pixels_hit")
 _NONE = np.uint64(0xffffffffffffffff)
 
@@ -74,8 +74,8 @@ DEFAULT_NEAR = cloud.DEFAULT_MIN_DEPTH       # what the fuser does not back-proj
 DEFAULT_FAR = 4.0 * cloud.DEFAULT_MAX_RANGE  # a view sees farther than one frame contributed
 DEFAULT_SPLAT = cloud.DEFAULT_VOXEL          # a point stands for its voxel
 
-MAX_SURFEL = 16                      # csrc/td_surfel.hip: TD_SURFEL_MAX; the largest pixel box of a disc is 33 x 33.  UNTUNED
-SURFEL_SLACK = 0.5 + 2.0 ** -10      # csrc/td_surfel.hip: TD_SURFEL_SLACK
+MAX_SURFEL = native.CONSTANTS["TD_SURFEL_MAX"]        # 16: the largest pixel box of a disc is 33 x 33.  UNTUNED
+SURFEL_SLACK = native.CONSTANTS["TD_SURFEL_SLACK"]    # 0.5 + 2.0 ** -10
 SURFEL_STATS = ("points", "out_of_range", "outside", "culled", "capped", "billboards", "drawn", "pixels_hit")
 SURFEL_FORMS = {"auto": 0, "thread": 1, "cooperative": 2}      # td_cloud_render_surfels' work distribution; the bits do not depend on it
 

@@ -27,8 +27,10 @@ import math
 import numpy as np
 import torch
 
+from . import native
+
 PRECISION_BITS = 22
-MAX_SIZES = 16          # csrc/td_resize.hip: TD_RESIZE_MAX_SIZES
+MAX_SIZES = native.CONSTANTS["TD_RESIZE_MAX_SIZES"]
 
 
 def _lanczos(t):
@@ -212,7 +214,6 @@ def lanczos_resize_hip(frames, meta, bank):
 
     A ``meta`` on the device is not read by the host (graph capture): an index outside the bank zero-fills that image and raises
     ``bank.status``.  A ``meta`` on the host is checked by the entry point (TD_ERR_BAD_ARG) and uploaded -- the eager / test form."""
-    from . import native
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[1] != 3:
         raise ValueError("frames must be uint8 [N,3,Hc,Wc]")
     if not frames.is_cuda:
