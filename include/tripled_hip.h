@@ -821,6 +821,56 @@ int td_cloud_views(const float* depth, const double* poses, TD_HOST const double
                    td_stream_t stream);
 
 /*
+ * Truncated signed distance fusion: surface points with oriented normals from depth maps and poses (csrc/td_tsdf.hip,
+ * tripled_amd/tsdf.py).  The reference has no such program: the statements are tsdf.samples_numpy and tsdf.surface_numpy, which the
+ * kernels equal bit for bit.  td_tsdf_samples writes (key, payload) pairs of td_cloud_keys' format, which the unchanged torch.sort /
+ * td_cloud_heads / cumsum / td_cloud_reduce_packed / merge chain sums into voxel rows; td_tsdf_surface reads the key-sorted rows.
+ * No TD_HOST parameter: inv_K is a DEVICE array.  An empty input (B = 0, V = 0) is a successful no-op without a launch.
+ *
+ * td_tsdf_samples: one launch.  depth, color, poses, stride, border, min_depth, max_range, edge, depth_scale, pose_scale, inv_voxel
+ *   (= 1 / voxel, computed once by the caller): as td_cloud_keys;  inv_K [9] float64 (device);  mask [B,H,W] uint8 or NULL: 0 drops
+ *   the pixel;  T: the band in voxels, 1 ... TD_TSDF_MAX_T.  A pixel is invalid by the first cause that holds: td_cloud_keys' causes
+ *   1 ... 4, then (5) its mask is 0.  For a valid pixel, float64, every operation rounded on its own (ray, p: td_cloud_keys'):
+ *     half = voxel 0.5;  trunc = (double)T voxel;  scale = 1048576.0 / trunc
+ *     for s = -2T ... 2T:   d_s = p_z + (double)s half;  f = d_s / ray_z;  sample = (ray_x f, ray_y f, ray_z f)
+ *       world = camera_to_world(sample)  (td_cloud_keys);  g = world inv_voxel;  i = floor(g);  k = the key of voxel i
+ *       the slot is skipped, by the first rule that holds: (range) k is invalid as in td_cloud_keys' cause 5; (duplicate) s > -2T and
+ *       k equals the key computed for slot s-1 (whether or not that slot was kept); (band) not |sdf| <= trunc, with
+ *         e_k = (i_k + 0.5) voxel - pose_scale t_k;  z_c = (r_02 e_0 + r_12 e_1) + r_22 e_2;  sdf = p_z - z_c
+ *       q = (long long)rint(sdf scale), clamped to [-2^20, 2^20];  payload = (q + 2^20) | r << 30 | g << 38 | b << 46
+ *   key, payload [4T+1][B H W] (out), slot-major: slot s of pixel p is element (s + 2T) B H W + p; INT64_MAX and 0 for a skipped slot
+ *   and for every slot of an invalid pixel.  A voxel's row after the reduction: w = count, S = (sum q_x + 1024 sum q_y + 2^20 sum q_z)
+ *   - 2^20 w, the summed distance in units of trunc / 2^20.
+ *   stats [TD_TSDF_SAMPLE_STATS] int64 (device) or NULL: incremented by the numbers of valid pixels, of pixels invalid by causes
+ *   1 ... 5, of slots kept, and of slots skipped as duplicate, by the band and by the range, in this order.
+ *   A thread owns 4, 2 or 1 consecutive columns of a row, as in td_cloud_keys (the mask's alignment counts too).
+ *   TD_ERR_BAD_ARG before any launch: a null depth, color, poses, inv_K, key or payload, B < 0, H or W < 1, T outside 1 ...
+ *   TD_TSDF_MAX_T, stride < 1, border < 0, voxel or inv_voxel not positive, edge negative or NaN.
+ *
+ * td_tsdf_surface: one launch, one thread per voxel.  keys [V] int64 ascending and unique, sums [V,7] int64 (the rows above).
+ *   D = (double)S / (double)w.  A voxel qualifies when w >= min_weight.  For voxel a and axis x, y, z: b = the voxel one step up the
+ *   axis (none when a's coordinate is 2^20 - 1; found by a binary search, for z by looking at the next key).  The edge crosses the
+ *   surface when a and b exist and qualify and (S_a >= 0) != (S_b >= 0).  Then, float64, every operation rounded on its own:
+ *     t = D_a / (D_a - D_b);  point_k = (float)((i_k + 0.5) voxel), on the edge's axis (float)(((i_k + 0.5) + t) voxel)
+ *     gradient of D at a voxel, per axis: (D_+ - D_-) / 2.0 where both neighbours qualify, D_+ - D or D - D_- where one does, else 0
+ *     g_k = (1.0 - t) ga_k + t gb_k;  n = sqrt((g_0 g_0 + g_1 g_1) + g_2 g_2);  normal_k = (float)(g_k / n), (0, 0, 0) when n = 0
+ *     colour: (2 sum_c + w) / (2 w), integer, of a if t < 0.5, else of b;  weight = min(w_a, w_b), saturating at int32
+ *   xyz, normal [V,3,3] float32, rgb [V,3,3] uint8, weight [V,3] int32 (out): written for (voxel, axis) where mask [V,3] uint8 (out,
+ *   always written) is 1.  stats [TD_TSDF_SURFACE_STATS] int64 (device) or NULL: incremented by the numbers of voxels under
+ *   min_weight, of crossings on x, y and z, and of crossings whose normal is (0, 0, 0).
+ *   TD_ERR_BAD_ARG before any launch: a null pointer other than stats, V < 0, voxel not positive, min_weight < 1.
+ */
+#define TD_TSDF_MAX_T 8              /* the widest band: 33 slots per pixel */
+#define TD_TSDF_SAMPLE_STATS 10
+#define TD_TSDF_SURFACE_STATS 5
+int td_tsdf_samples(const float* depth, const uint8_t* color, const double* poses, const double* inv_K, const uint8_t* mask, int B, int H,
+                    int W, int T, double depth_scale, double pose_scale, double voxel, double inv_voxel, int stride, int border,
+                    double min_depth, double max_range, float edge, long long* key, unsigned long long* payload, long long* stats,
+                    td_stream_t stream);
+int td_tsdf_surface(const long long* keys, const long long* sums, long long V, double voxel, long long min_weight, float* xyz,
+                    float* normal, uint8_t* rgb, int* weight, uint8_t* mask, long long* stats, td_stream_t stream);
+
+/*
  * KITTI ground-truth depth maps from velodyne scans, a batch of frames of different sizes per call (csrc/td_velo.hip,
  * tripled_amd/velodyne.py).  Replaces generate_depth_map, mono/datasets/kitti_utils.py:50-102 (the projection :71-86, the last-write
  * scatter :89-90, the duplicate rule with sub2ind :43-47,93-99, the clamp :100), which KITTIRAWDataset.get_depth calls per frame,

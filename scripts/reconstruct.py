@@ -5,7 +5,7 @@ voxel-averaged coloured point cloud (binary PLY: x y z float, red green blue uch
   python scripts/reconstruct.py --config config/cfg_kitti_tripleD.py --checkpoint work/epoch_20.pth --data_path /data/kitti_odom \
          --sequence 9 [--frames A:B] [--poses FILE] [--voxel V] [--stride S] [--border P] [--max_range R] [--edge E] [--min_count N] \
          [--min_views M] [--view_radius R] [--view_tol T] [--depth_scale S] [--pose_scale S] [--batch_size 12] [--precision bf16] \
-         [--post_process] [--device cpu] [--save_poses FILE] --out cloud.ply
+         [--post_process] [--device cpu] [--save_poses FILE] [--tsdf [--trunc_voxels 3] [--min_weight 2]] --out cloud.ply
 
 Frames: <data_path>/sequences/NN/image_0/%06d.png; the frame count is the line count of <data_path>/poses/NN.txt (or of --poses).
 Without --poses the model's own poses are used (depth and pose share the model's scale); --poses FILE takes camera-to-world poses
@@ -17,6 +17,12 @@ the last line is the consistency rate, the kept pixels over the tested ones: a f
 The work is tripled_amd.cloud.SceneFuser (csrc/td_cloud.hip and csrc/td_views.hip on a HIP device); without --min_views the last
 line printed is the statistics.  --save_poses FILE writes the camera-to-world poses that were fused (the model's own, or --poses')
 in KITTI pose text: what scripts/render_cloud.py needs to look at the cloud from where the frames were taken.
+--tsdf fuses truncated signed distances instead of averaging points per voxel (tripled_amd.tsdf.TsdfFuser, csrc/td_tsdf.hip): every
+pixel adds its signed distance to the voxels its ray meets within --trunc_voxels voxels of its surface, and the PLY holds one point
+per voxel edge on which the averaged distance changes sign, between voxels of at least --min_weight samples (both untuned starting
+values), with nx ny nz after count: unit normals that face where the surface was seen from, so render_cloud.py --surfels and
+eval_cloud.py use them as they are.  count holds the edge's weight.  --min_count does not apply; --min_views composes through the
+per-pixel mask.  Without --tsdf nothing of this runs and the output is what it always was.
 """
 import argparse
 import os
@@ -30,7 +36,7 @@ import tripled_amd  # noqa: F401,E402
 from mmcv import Config  # noqa: E402
 from mono.datasets.kitti_dataset import KITTIOdomDataset, odom_sequence_files  # noqa: E402
 from mono.model import MONO  # noqa: E402
-from tripled_amd import cloud, odometry  # noqa: E402
+from tripled_amd import cloud, odometry, tsdf  # noqa: E402
 
 
 def main():
@@ -61,6 +67,9 @@ def main():
     ap.add_argument("--post_process", action="store_true")
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--save_poses", default=None, help="write the poses that were fused, in KITTI pose text")
+    ap.add_argument("--tsdf", action="store_true", help="fuse truncated signed distances: surface points with oriented normals")
+    ap.add_argument("--trunc_voxels", type=int, default=tsdf.DEFAULT_TRUNC_VOXELS, help="the band on either side of a surface, in voxels (untuned)")
+    ap.add_argument("--min_weight", type=int, default=tsdf.DEFAULT_MIN_WEIGHT, help="samples a voxel needs to take part in the surface (untuned)")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
     cfg = Config.fromfile(args.config)
@@ -79,22 +88,28 @@ def main():
         frames = (int(a or 0), int(b or n_frames))
     dataset = KITTIOdomDataset(args.data_path, odom_sequence_files(args.sequence, n_frames), height, width, [0, 1], is_train=False,
                                img_ext=args.img_ext)
-    fuser = cloud.SceneFuser(model, height, width, args.device, voxel=args.voxel, batch_size=args.batch_size, precision=args.precision,
-                             stride=args.stride, border=args.border, min_depth=args.min_depth, max_range=args.max_range, edge=args.edge,
-                             min_count=args.min_count, depth_scale=args.depth_scale, pose_scale=args.pose_scale,
-                             post_process=args.post_process, min_views=args.min_views, view_radius=args.view_radius,
-                             view_tol=args.view_tol)
+    shared = dict(voxel=args.voxel, batch_size=args.batch_size, precision=args.precision, stride=args.stride, border=args.border,
+                  min_depth=args.min_depth, max_range=args.max_range, edge=args.edge, depth_scale=args.depth_scale,
+                  pose_scale=args.pose_scale, post_process=args.post_process, min_views=args.min_views, view_radius=args.view_radius,
+                  view_tol=args.view_tol)
+    if args.tsdf:
+        fuser = tsdf.TsdfFuser(model, height, width, args.device, trunc_voxels=args.trunc_voxels, min_weight=args.min_weight, **shared)
+    else:
+        fuser = cloud.SceneFuser(model, height, width, args.device, min_count=args.min_count, **shared)
     print("-> Fusing sequence %02d: frames %s of %d" % (args.sequence, "%d:%d" % frames if frames else "0:%d" % n_frames, n_frames))
     result = fuser.fuse(dataset, poses=poses, frames=frames)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    cloud.save_ply(args.out, result.xyz, result.rgb, result.count)
-    print("saved %d points to %s" % (len(result.keys), args.out))
+    if args.tsdf:
+        cloud.save_ply(args.out, result.xyz, result.rgb, result.weight, normals=result.normal)
+    else:
+        cloud.save_ply(args.out, result.xyz, result.rgb, result.count)
+    print("saved %d points to %s" % (len(result.xyz), args.out))
     if args.save_poses:
         os.makedirs(os.path.dirname(os.path.abspath(args.save_poses)), exist_ok=True)
         odometry.save_kitti_poses(args.save_poses, fuser.poses)
         print("saved %d poses to %s" % (len(fuser.poses), args.save_poses))
     print(" ".join("%s %d" % (k, v) for k, v in result.stats.items()))
-    if args.min_views:
+    if args.min_views and not args.tsdf:
         kept, tested = result.stats["valid"], result.stats["valid"] + result.stats["invalid_views"]
         print("consistency rate %.4f (%d of %d tested pixels have %d views or more)" % (kept / max(tested, 1), kept, tested, args.min_views))
 

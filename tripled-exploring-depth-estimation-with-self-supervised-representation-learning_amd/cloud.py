@@ -183,19 +183,13 @@ def camera_points_numpy(depth, inv_K, depth_scale=1.0):
         return np.stack([ds * ((m[3 * k] * u + m[3 * k + 1] * v) + m[3 * k + 2]) for k in range(3)], 0)
 
 
-def keys_numpy(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_voxel=1.0 / DEFAULT_VOXEL, stride=1, border=0,
-               min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=0.0):
-    """depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4] -> (key int64 [B H W], payload uint64 [B H W], counts
-    int64 [6] in the order of CAUSES).  The statement td_cloud_keys is tested against, operation for operation."""
-    d = np.ascontiguousarray(depth, dtype=np.float32)
-    c = np.ascontiguousarray(color, dtype=np.uint8)
-    P = np.ascontiguousarray(poses, dtype=np.float64)
-    if d.ndim != 3 or c.shape != (d.shape[0], 3) + d.shape[1:] or P.shape != (d.shape[0], 3, 4):
-        raise ValueError("depth [B,H,W], color [B,3,H,W], poses [B,3,4]; got %s, %s, %s" % (d.shape, c.shape, P.shape))
-    m = _inv_K9(inv_K)
+def pixel_causes_numpy(depth, depth_scale, stride, border, min_depth, max_range, edge):
+    """depth float32 [B,H,W] -> int8 [B,H,W]: 0 for a pixel that is valid so far, else the first of td_cloud_keys' causes 1 ... 4 that
+    holds (off the stride's lattice, in the border, depth not finite or out of range, a depth step to a 4-neighbour).  Shared by
+    keys_numpy and tsdf.samples_numpy."""
+    d = np.asarray(depth, dtype=np.float32)
     B, H, W = d.shape
     stride, border = int(stride), int(border)
-    depth_scale, pose_scale, inv_voxel = np.float64(depth_scale), np.float64(pose_scale), np.float64(inv_voxel)
     ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
     ys, xs = np.broadcast_to(ys, d.shape), np.broadcast_to(xs, d.shape)
     cause = np.zeros(d.shape, np.int8)
@@ -204,7 +198,7 @@ def keys_numpy(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_
         cause[(cause == 0) & mask] = code
 
     with np.errstate(invalid="ignore", over="ignore"):
-        ds = d.astype(np.float64) * depth_scale
+        ds = d.astype(np.float64) * np.float64(depth_scale)
         mark((xs % stride != 0) | (ys % stride != 0), 1)
         mark((xs < border) | (xs >= W - border) | (ys < border) | (ys >= H - border), 2)
         mark(~np.isfinite(d) | ~((ds >= np.float64(min_depth)) & (ds <= np.float64(max_range))), 3)
@@ -219,6 +213,28 @@ def keys_numpy(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_
                 inside[tuple(edge_line)] = False           # the rolled-in line is no neighbour
                 bad |= inside & (~np.isfinite(nb) | (np.abs(d - nb) > e * np.minimum(d, nb)))
             mark(bad, 4)
+    return cause
+
+
+def keys_numpy(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_voxel=1.0 / DEFAULT_VOXEL, stride=1, border=0,
+               min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=0.0):
+    """depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4] -> (key int64 [B H W], payload uint64 [B H W], counts
+    int64 [6] in the order of CAUSES).  The statement td_cloud_keys is tested against, operation for operation."""
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    c = np.ascontiguousarray(color, dtype=np.uint8)
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    if d.ndim != 3 or c.shape != (d.shape[0], 3) + d.shape[1:] or P.shape != (d.shape[0], 3, 4):
+        raise ValueError("depth [B,H,W], color [B,3,H,W], poses [B,3,4]; got %s, %s, %s" % (d.shape, c.shape, P.shape))
+    m = _inv_K9(inv_K)
+    B, H, W = d.shape
+    stride, border = int(stride), int(border)
+    depth_scale, pose_scale, inv_voxel = np.float64(depth_scale), np.float64(pose_scale), np.float64(inv_voxel)
+    cause = pixel_causes_numpy(d, depth_scale, stride, border, min_depth, max_range, edge)
+
+    def mark(mask, code):
+        cause[(cause == 0) & mask] = code
+
+    with np.errstate(invalid="ignore", over="ignore"):
         px, py, pz = camera_points_numpy(d, m, depth_scale)
         g = []
         for k in range(3):

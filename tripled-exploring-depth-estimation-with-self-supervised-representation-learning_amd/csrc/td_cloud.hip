@@ -33,29 +33,6 @@ struct CloudKeyArgs {
   unsigned long long* stats;   // [6] or NULL: += valid, off-lattice, border, depth, edge, range
 };
 
-// VEC consecutive elements as one access (the caller guarantees sizeof(T) * VEC alignment)
-template <int VEC, typename T>
-__device__ __forceinline__ void load_run(const T* __restrict__ p, T* out) {
-  struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
-  const Pack pk = *reinterpret_cast<const Pack*>(p);
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) out[j] = pk.v[j];
-}
-
-template <int VEC, typename T>
-__device__ __forceinline__ void store_run(T* __restrict__ p, const T* in) {
-  struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
-  Pack pk;
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) pk.v[j] = in[j];
-  *reinterpret_cast<Pack*>(p) = pk;
-}
-
-// the flying-pixel test against one neighbour, float32 on the unscaled depths
-__device__ __forceinline__ bool edge_bad(float d, float nb, float edge) {
-  return !isfinite(nb) || fabsf(d - nb) > edge * fminf(d, nb);
-}
-
 // A thread owns VEC consecutive columns of one row; VEC divides W, so the flat pixel index of chunk c is c * VEC and a wave's
 // loads and stores are contiguous.  The rows above and below are read with the same alignment; the left and right neighbours of
 // the run are two scalar loads that the neighbouring threads' lines already hold.

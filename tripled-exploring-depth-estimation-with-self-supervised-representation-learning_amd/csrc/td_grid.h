@@ -1,4 +1,4 @@
-// What the cloud kernels share (td_cloud, td_scan, td_views, td_nn, td_normals): the voxel / cell key, the pieces of the walk over a grid of
+// What the cloud kernels share (td_cloud, td_tsdf, td_scan, td_views, td_nn, td_normals): the voxel / cell key, the pieces of the walk over a grid of
 // cells sorted by it, and the camera-to-world transform.  Every user is built with -ffp-contract=off: each float64 product and sum below is
 // rounded on its own, as the numpy statements (cloud.grid_keys_numpy, cloud_eval.walk_numpy) round it.
 #pragma once
@@ -45,6 +45,31 @@ __device__ __forceinline__ void camera_to_world(const double* __restrict__ P, do
   wx = ((P[0] * x + P[1] * y) + P[2] * z) + scale * P[3];
   wy = ((P[4] * x + P[5] * y) + P[6] * z) + scale * P[7];
   wz = ((P[8] * x + P[9] * y) + P[10] * z) + scale * P[11];
+}
+
+// What the per-pixel kernels share (td_cloud_keys, td_tsdf_samples): a thread's run of columns as one access, and the flying-pixel test.
+
+// VEC consecutive elements as one access (the caller guarantees sizeof(T) * VEC alignment)
+template <int VEC, typename T>
+__device__ __forceinline__ void load_run(const T* __restrict__ p, T* out) {
+  struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
+  const Pack pk = *reinterpret_cast<const Pack*>(p);
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) out[j] = pk.v[j];
+}
+
+template <int VEC, typename T>
+__device__ __forceinline__ void store_run(T* __restrict__ p, const T* in) {
+  struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
+  Pack pk;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) pk.v[j] = in[j];
+  *reinterpret_cast<Pack*>(p) = pk;
+}
+
+// the flying-pixel test against one neighbour, float32 on the unscaled depths
+__device__ __forceinline__ bool edge_bad(float d, float nb, float edge) {
+  return !isfinite(nb) || fabsf(d - nb) > edge * fminf(d, nb);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

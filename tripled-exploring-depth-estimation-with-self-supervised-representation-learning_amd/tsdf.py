@@ -1,0 +1,585 @@
+"""Truncated signed distance fusion: the depth maps and camera poses of a sequence fused into surface points with oriented normals.
+
+cloud.py averages points per voxel: depth noise along the ray spreads one surface over several voxel layers, and the cloud keeps no
+record of the side a surface was seen from.  Here every pixel adds a signed distance to the voxels its ray meets in a band around its
+surface; the surface is where the averaged distance changes sign, and the gradient of that field is a normal that points at the
+observer (Curless & Levoy 1996; KinectFusion).  The reference has no such program.
+
+Scatter, not gather: a frame updates exactly the voxels its own rays sample, through the same store / sort / sum-per-destination chain
+as cloud.py (td_cloud_heads, td_cloud_reduce_packed, merge_hip, all unchanged).  That chain's sums are linear in the payload's fields,
+so a sample's distance rides in the 30 offset bits as an offset-binary integer v = q + 2^20, and sum v = sum q_x + 1024 sum q_y + 2^20
+sum q_z.  Everything accumulated is an integer: the map is bit-identical from run to run and does not depend on how the sequence is
+cut into batches or a batch's pairs into sub-chunks.
+
+Three layers, as in cloud.py:
+  * host statements in numpy (``samples_numpy``, ``surface_numpy``, ``fuse_tsdf_numpy``): the ``device='cpu'`` path and what the kernels
+    are tested against, operation for operation; ``samples_bruteforce`` / ``surface_bruteforce`` (plain Python floats and a dict) pin them;
+  * ``samples_hip``, ``surface_hip``, ``fuse_tsdf_hip`` (csrc/td_tsdf.hip): device tensors only, a CPU tensor is an error;
+  * ``TsdfFuser``: frames of a dataset -> SceneFuser's depth and pose plumbing -> the surface.
+
+The exact arithmetic (float64; every operation rounded on its own).  A pixel is valid by td_cloud_keys' causes 1 ... 4 (cloud.py) and
+then its mask.  ray, p: cloud.py's.  With half = voxel 0.5, trunc = float(T) voxel, scale = 1048576.0 / trunc, for s = -2T ... 2T:
+    d_s = p_z + float(s) half;   f = d_s / ray_z;   sample_k = ray_k f
+    world_k = ((r_k0 sample_x + r_k1 sample_y) + r_k2 sample_z) + pose_scale t_k;   g = world inv_voxel;   i = floor(g)
+    skipped by the first rule that holds:  range: i outside [-2^20, 2^20) or the sentinel voxel;  duplicate: s > -2T and i is the
+    voxel computed for slot s-1 (a ray meets a voxel in one interval, so equal voxels are consecutive);  band: not |sdf| <= trunc with
+    e_k = (i_k + 0.5) voxel - pose_scale t_k;   z_c = (r_02 e_0 + r_12 e_1) + r_22 e_2;   sdf = p_z - z_c
+    q = rint(sdf scale) clamped to [-2^20, 2^20];   payload = (q + 2^20) | r << 30 | g << 38 | b << 46
+This is a defined sampling at half-voxel steps of depth along the ray, not a voxel traversal: a voxel whose corner the ray clips
+between two samples is missed.  sdf is projective (along the camera's z), positive between the camera and the surface.
+A voxel's row: w = count, S = (sum q_x + 1024 sum q_y + 2^20 sum q_z) - 2^20 w (exact), D = S / w in units of trunc / 2^20.  The
+surface (``surface_numpy``'s docstring) lies on the +x / +y / +z edges between voxels of weight >= min_weight whose S differ in sign.
+"""
+import collections
+import math
+
+import numpy as np
+import torch
+
+from . import cloud, native
+from .cloud import HALF, INVALID_KEY
+
+MAX_T = native.CONSTANTS["TD_TSDF_MAX_T"]
+ONE = 1 << 20                          # trunc as an integer
+SAMPLE_STATS = ("valid", "invalid_stride", "invalid_border", "invalid_depth", "invalid_edge", "invalid_mask", "samples",
+                "skipped_duplicate", "skipped_band", "skipped_range")
+SURFACE_STATS = ("voxels_under_min_weight", "crossings_x", "crossings_y", "crossings_z", "crossings_without_normal")
+assert len(SAMPLE_STATS) == native.CONSTANTS["TD_TSDF_SAMPLE_STATS"] and len(SURFACE_STATS) == native.CONSTANTS["TD_TSDF_SURFACE_STATS"]
+
+# UNTUNED starting values: nobody has looked at a surface of a trained checkpoint with them.
+DEFAULT_TRUNC_VOXELS = 3
+DEFAULT_MIN_WEIGHT = 2
+DEFAULT_PAIR_CHUNK = 1 << 25           # pairs sorted at a time (16 bytes each, and the sort's own buffers)
+
+Surface = collections.namedtuple("Surface", "xyz normal rgb weight stats")
+Surface.__doc__ = """xyz float32 [n,3], normal float32 [n,3] (unit, facing where the surface was seen from; (0, 0, 0): none), rgb uint8
+[n,3], weight int32 [n] (the smaller sample count of the edge's two voxels, saturating), in (voxel, axis) order of the key-sorted map,
+on the fuser's device (numpy arrays on the host path);  stats: dict of Python ints: points (pixels seen), SAMPLE_STATS, voxels,
+SURFACE_STATS, surface_points."""
+
+
+def _check(T, voxel, min_weight=1):
+    if not 1 <= int(T) <= MAX_T:
+        raise ValueError("trunc_voxels: 1 ... %d, got %r" % (MAX_T, T))
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError("voxel: a positive size, got %r" % (voxel,))
+    if int(min_weight) < 1:
+        raise ValueError("min_weight: at least 1, got %r" % (min_weight,))
+
+
+def row_sdf_sum(sums):
+    """int64 rows [V,7] -> S int64 [V] = (sum q_x + 1024 sum q_y + 2^20 sum q_z) - 2^20 count, exact."""
+    s = np.asarray(sums, np.int64).reshape(-1, 7)
+    return (s[:, 1] + 1024 * s[:, 2] + ONE * s[:, 3]) - ONE * s[:, 0]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# host statements
+
+def samples_numpy(depth, color, poses, inv_K, T, voxel, mask=None, depth_scale=1.0, pose_scale=1.0, stride=1, border=0,
+                  min_depth=cloud.DEFAULT_MIN_DEPTH, max_range=cloud.DEFAULT_MAX_RANGE, edge=0.0):
+    """depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4], mask [B,H,W] (0 drops the pixel) or None -> (key int64
+    [(4T+1) B H W], payload uint64 [(4T+1) B H W], slot-major, counts int64 [10] in the order of SAMPLE_STATS).  The statement
+    td_tsdf_samples is tested against, operation for operation (the module's docstring)."""
+    d = np.ascontiguousarray(depth, dtype=np.float32)
+    c = np.ascontiguousarray(color, dtype=np.uint8)
+    P = np.ascontiguousarray(poses, dtype=np.float64)
+    if d.ndim != 3 or c.shape != (d.shape[0], 3) + d.shape[1:] or P.shape != (d.shape[0], 3, 4):
+        raise ValueError("depth [B,H,W], color [B,3,H,W], poses [B,3,4]; got %s, %s, %s" % (d.shape, c.shape, P.shape))
+    _check(T, voxel)
+    T = int(T)
+    m = cloud._inv_K9(inv_K)
+    B, H, W = d.shape
+    voxel, depth_scale, pose_scale = np.float64(voxel), np.float64(depth_scale), np.float64(pose_scale)
+    inv_voxel = np.float64(1.0 / float(voxel))
+    cause = cloud.pixel_causes_numpy(d, depth_scale, stride, border, min_depth, max_range, edge)
+    if mask is not None:
+        mk = np.asarray(mask)
+        if mk.shape != d.shape:
+            raise ValueError("mask: %s like the depth, got %s" % (d.shape, mk.shape))
+        cause[(cause == 0) & (mk == 0)] = 5
+    ok = cause == 0
+    counts = np.zeros(len(SAMPLE_STATS), np.int64)
+    counts[:6] = np.bincount(cause.reshape(-1), minlength=6)
+    v, u = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    ray = [(m[3 * k] * u + m[3 * k + 1] * v) + m[3 * k + 2] for k in range(3)]
+    R = [[P[:, k, j].reshape(B, 1, 1) for j in range(4)] for k in range(3)]
+    rgb = (c[:, 0].astype(np.uint64) << np.uint64(30)) | (c[:, 1].astype(np.uint64) << np.uint64(38)) | (c[:, 2].astype(np.uint64) << np.uint64(46))
+    half = voxel * np.float64(0.5)
+    trunc = np.float64(T) * voxel
+    scale = np.float64(1048576.0) / trunc
+    keys, payloads = [], []
+    prev = np.full(d.shape, INVALID_KEY, np.int64)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        pz = (d.astype(np.float64) * depth_scale) * ray[2]
+        for s in range(-2 * T, 2 * T + 1):
+            dz = pz + np.float64(s) * half
+            f = dz / ray[2]
+            sample = [ray[k] * f for k in range(3)]
+            g = [(((R[k][0] * sample[0] + R[k][1] * sample[1]) + R[k][2] * sample[2]) + pose_scale * R[k][3]) * inv_voxel for k in range(3)]
+            key = cloud.grid_keys_numpy(g)[0]
+            out_of_range = ok & (key == INVALID_KEY)
+            duplicate = ok & ~out_of_range & (key == prev) if s > -2 * T else np.zeros(d.shape, bool)
+            rest = ok & ~out_of_range & ~duplicate
+            e = [(np.floor(g[k]) + 0.5) * voxel - pose_scale * R[k][3] for k in range(3)]
+            zc = (R[0][2] * e[0] + R[1][2] * e[1]) + R[2][2] * e[2]
+            sdf = pz - zc
+            inside = rest & (np.abs(sdf) <= trunc)
+            q = np.clip(np.rint(np.where(inside, sdf * scale, 0.0)), -ONE, ONE).astype(np.int64)
+            keys.append(np.where(inside, key, INVALID_KEY).astype(np.int64).reshape(-1))
+            payloads.append(np.where(inside, (q + ONE).astype(np.uint64) | rgb, np.uint64(0)).astype(np.uint64).reshape(-1))
+            counts[6] += inside.sum()
+            counts[7] += duplicate.sum()
+            counts[8] += (rest & ~inside).sum()
+            counts[9] += out_of_range.sum()
+            prev = np.where(ok, key, prev)
+    return np.concatenate(keys), np.concatenate(payloads), counts
+
+
+def _neighbour_numpy(keys, axis, direction):
+    """The index of every voxel's neighbour one step along ``axis`` in ``direction`` = +-1 in the ascending unique ``keys``, -1 where
+    there is none.  The coordinate field is tested first: nothing is carried into the next field."""
+    shift = (42, 21, 0)[axis]
+    mask = 2 * HALF - 1
+    field = (keys >> shift) & mask
+    edge = field == (mask if direction > 0 else 0)
+    kb = np.where(edge, 0, keys + direction * (1 << shift))
+    edge |= kb == INVALID_KEY
+    at = np.searchsorted(keys, kb)
+    found = ~edge & (at < len(keys))
+    found &= keys[np.minimum(at, max(len(keys) - 1, 0))] == kb
+    return np.where(found, at, -1)
+
+
+def surface_numpy(keys, sums, voxel, min_weight=DEFAULT_MIN_WEIGHT):
+    """keys int64 [V] ascending and unique, sums int64 [V,7] -> (xyz float32 [V,3,3], normal float32 [V,3,3], rgb uint8 [V,3,3], weight
+    int32 [V,3], mask bool [V,3], counts int64 [5] in the order of SURFACE_STATS): slot (a, axis) holds the crossing on the edge from
+    voxel a one step up the axis; where mask is False the slot is zero.  The statement td_tsdf_surface is tested against.
+
+    D = float64(S) / float64(w).  A voxel qualifies when w >= min_weight.  The edge a -> b crosses when both exist and qualify and
+    (S_a >= 0) != (S_b >= 0) (integers; zero counts as positive).  Then t = D_a / (D_a - D_b); the point is (i_a + 0.5) voxel, on the
+    edge's axis ((i_a + 0.5) + t) voxel, as float32; the colour is the rounded mean colour of a if t < 0.5, else of b; the weight is
+    min(w_a, w_b), saturating; the normal is g / |g| with g = (1.0 - t) g_a + t g_b, |g| = sqrt((g_0 g_0 + g_1 g_1) + g_2 g_2), and the
+    gradient of D at a voxel is per axis (D_+ - D_-) / 2.0 where both neighbours qualify, D_+ - D or D - D_- where one does, else 0.
+    D is positive on the camera's side, so the normal faces where the surface was seen from."""
+    keys, sums = np.asarray(keys, np.int64).reshape(-1), np.asarray(sums, np.int64).reshape(-1, 7)
+    _check(1, voxel, min_weight)
+    V = len(keys)
+    if len(sums) != V or (V > 1 and not np.all(np.diff(keys) > 0)):
+        raise ValueError("keys [V] ascending and unique, sums [V,7]")
+    voxel = np.float64(voxel)
+    xyz, normal = np.zeros((V, 3, 3), np.float32), np.zeros((V, 3, 3), np.float32)
+    rgb, weight, mask = np.zeros((V, 3, 3), np.uint8), np.zeros((V, 3), np.int32), np.zeros((V, 3), bool)
+    counts = np.zeros(len(SURFACE_STATS), np.int64)
+    if V == 0:
+        return xyz, normal, rgb, weight, mask, counts
+    w, S = sums[:, 0], row_sdf_sum(sums)
+    qualifies = w >= int(min_weight)
+    counts[0] = (~qualifies).sum()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        D = S.astype(np.float64) / w.astype(np.float64)
+        G = np.zeros((V, 3))
+        up = []
+        for axis in range(3):
+            p, m = _neighbour_numpy(keys, axis, 1), _neighbour_numpy(keys, axis, -1)
+            up.append(p)
+            hp, hm = (p >= 0) & qualifies[np.maximum(p, 0)], (m >= 0) & qualifies[np.maximum(m, 0)]
+            Dp, Dm = D[np.maximum(p, 0)], D[np.maximum(m, 0)]
+            G[:, axis] = np.where(hp & hm, (Dp - Dm) / 2.0, np.where(hp, Dp - D, np.where(hm, D - Dm, 0.0)))
+        i = np.stack(cloud.unpack_key(keys), -1).astype(np.float64)
+        colour = ((2 * sums[:, 4:7] + w[:, None]) // np.maximum(2 * w[:, None], 1)).astype(np.uint8)
+        for axis in range(3):
+            b = np.maximum(up[axis], 0)
+            cross = (up[axis] >= 0) & qualifies & qualifies[b] & ((S >= 0) != (S[b] >= 0))
+            t = np.where(cross, D / (D - D[b]), 0.0)
+            g = [(1.0 - t) * G[:, k] + t * G[b, k] for k in range(3)]
+            norm = np.sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2])
+            has = cross & (norm > 0.0)
+            for k in range(3):
+                normal[:, axis, k] = np.where(has, g[k] / norm, 0.0).astype(np.float32)
+                centre = i[:, k] + 0.5
+                xyz[:, axis, k] = np.where(cross, ((centre + t) if k == axis else centre) * voxel, 0.0).astype(np.float32)
+            rgb[:, axis] = np.where(cross[:, None], np.where((t < 0.5)[:, None], colour, colour[b]), 0)
+            weight[:, axis] = np.where(cross, np.minimum(np.minimum(w, w[b]), 0x7fffffff), 0).astype(np.int32)
+            mask[:, axis] = cross
+            counts[1 + axis] = cross.sum()
+            counts[4] += (cross & ~has).sum()
+    return xyz, normal, rgb, weight, mask, counts
+
+
+def _stats(sample_counts, voxels, surface_counts, n_points):
+    out = {"points": int(np.sum(sample_counts[:6]))}
+    out.update({name: int(v) for name, v in zip(SAMPLE_STATS, sample_counts)})
+    out["voxels"] = int(voxels)
+    out.update({name: int(v) for name, v in zip(SURFACE_STATS, surface_counts)})
+    out["surface_points"] = int(n_points)
+    return out
+
+
+def _view_mask_numpy(depth, poses, inv_K, K, min_views, view_radius, view_tol, depth_scale, pose_scale, min_depth, max_range, mask):
+    """The multi-view filter as a per-pixel mask: cloud.views_numpy's votes >= min_views, and the caller's mask."""
+    votes = cloud.views_numpy(depth, poses, inv_K, cloud._view_K9(K, inv_K), view_radius, view_tol, depth_scale, pose_scale, min_depth,
+                              max_range)
+    keep = votes >= int(min_views)
+    return keep if mask is None else keep & (np.asarray(mask) != 0)
+
+
+def fuse_tsdf_numpy(depth, color, poses, inv_K, voxel=cloud.DEFAULT_VOXEL, trunc_voxels=DEFAULT_TRUNC_VOXELS,
+                    min_weight=DEFAULT_MIN_WEIGHT, stride=1, border=0, min_depth=cloud.DEFAULT_MIN_DEPTH,
+                    max_range=cloud.DEFAULT_MAX_RANGE, edge=0.0, depth_scale=1.0, pose_scale=1.0, mask=None, min_views=0,
+                    view_radius=cloud.DEFAULT_VIEW_RADIUS, view_tol=cloud.DEFAULT_VIEW_TOL, K=None, debug=None):
+    """All frames at once -> Surface of numpy arrays: samples_numpy (with ``min_views`` > 0 behind the mask votes >= min_views of
+    cloud.views_numpy over all frames), cloud.voxel_table_numpy, surface_numpy, then a boolean select in (voxel, axis) order.
+    ``debug``: a dict that receives the map's "keys" and "sums"."""
+    cloud._check_params(voxel, stride, border, min_depth, max_range, edge)
+    cloud._check_view_params(min_views, view_radius, view_tol)
+    _check(trunc_voxels, voxel, min_weight)
+    if min_views > 0:
+        mask = _view_mask_numpy(depth, poses, inv_K, K, min_views, view_radius, view_tol, depth_scale, pose_scale, min_depth, max_range, mask)
+    key, payload, counts = samples_numpy(depth, color, poses, inv_K, trunc_voxels, voxel, mask, depth_scale, pose_scale, stride, border,
+                                         min_depth, max_range, edge)
+    keys, sums = cloud.voxel_table_numpy(key, payload)
+    if debug is not None:
+        debug["keys"], debug["sums"] = keys, sums
+    xyz, normal, rgb, weight, hit, scounts = surface_numpy(keys, sums, voxel, min_weight)
+    return Surface(xyz[hit], normal[hit], rgb[hit], weight[hit], _stats(counts, len(keys), scounts, int(hit.sum())))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the literal brute forces: plain Python floats (IEEE float64, one rounding per operation) and a dict
+
+def samples_bruteforce(depth, color, poses, inv_K, T, voxel, mask=None, depth_scale=1.0, pose_scale=1.0, stride=1, border=0, min_depth=0.1,
+                       max_range=1.0, edge=0.0):
+    """One pixel and one slot at a time -> (table: dict (ix, iy, iz) -> [count, sum of v = q + 2^20, sum r, sum g, sum b], counts list
+    [10] in the order of SAMPLE_STATS).  float32 only where the edge filter compares depths."""
+    B, H, W = depth.shape
+    m = [float(x) for x in np.asarray(inv_K, np.float64)[:3, :3].reshape(-1)]
+    voxel, depth_scale, pose_scale = float(voxel), float(depth_scale), float(pose_scale)
+    inv_voxel = 1.0 / voxel
+    half, trunc = voxel * 0.5, float(T) * voxel
+    scale = 1048576.0 / trunc
+    table, counts = {}, [0] * len(SAMPLE_STATS)
+    for b in range(B):
+        P = [[float(x) for x in row] for row in poses[b]]
+        for y in range(H):
+            for x in range(W):
+                d32 = depth[b, y, x]
+                ds = float(d32) * depth_scale
+                if x % stride or y % stride:
+                    counts[1] += 1
+                    continue
+                if x < border or x >= W - border or y < border or y >= H - border:
+                    counts[2] += 1
+                    continue
+                if not math.isfinite(float(d32)) or not (min_depth <= ds <= max_range):
+                    counts[3] += 1
+                    continue
+                if edge > 0:
+                    bad = False
+                    for yy, xx in ((y - 1, x), (y + 1, x), (y, x - 1), (y, x + 1)):
+                        if 0 <= yy < H and 0 <= xx < W:
+                            nb = depth[b, yy, xx]
+                            if not math.isfinite(float(nb)) or np.float32(abs(np.float32(d32 - nb))) > np.float32(edge) * min(d32, nb):
+                                bad = True
+                    if bad:
+                        counts[4] += 1
+                        continue
+                if mask is not None and not mask[b, y, x]:
+                    counts[5] += 1
+                    continue
+                counts[0] += 1
+                u, v = float(x), float(y)
+                ray = [(m[3 * k] * u + m[3 * k + 1] * v) + m[3 * k + 2] for k in range(3)]
+                pz = ds * ray[2]
+                prev = None
+                for s in range(-2 * T, 2 * T + 1):
+                    dz = pz + float(s) * half
+                    try:
+                        f = dz / ray[2]
+                    except ZeroDivisionError:
+                        f = math.nan
+                    sample = [r * f for r in ray]
+                    g = [(((P[k][0] * sample[0] + P[k][1] * sample[1]) + P[k][2] * sample[2]) + pose_scale * P[k][3]) * inv_voxel
+                         for k in range(3)]
+                    if not all(math.isfinite(t) and -HALF <= math.floor(t) < HALF for t in g):
+                        counts[9] += 1
+                        prev = None
+                        continue
+                    i = tuple(int(math.floor(t)) for t in g)
+                    if i == (HALF - 1,) * 3:
+                        counts[9] += 1
+                        prev = None
+                        continue
+                    if i == prev:
+                        counts[7] += 1
+                        continue
+                    prev = i
+                    e = [(float(i[k]) + 0.5) * voxel - pose_scale * P[k][3] for k in range(3)]
+                    zc = (P[0][2] * e[0] + P[1][2] * e[1]) + P[2][2] * e[2]
+                    sdf = pz - zc
+                    if not abs(sdf) <= trunc:
+                        counts[8] += 1
+                        continue
+                    q = max(-ONE, min(ONE, int(round(sdf * scale))))          # round: half to even, as rint
+                    row = table.setdefault(i, [0] * 5)
+                    row[0] += 1
+                    row[1] += q + ONE
+                    for ch in range(3):
+                        row[2 + ch] += int(color[b, ch, y, x])
+                    counts[6] += 1
+    return table, counts
+
+
+def surface_bruteforce(table, voxel, min_weight):
+    """table: dict (ix, iy, iz) -> (w, S, sum r, sum g, sum b) with S the exact summed distance -> a list, in (voxel, axis) order of the
+    sorted voxels, of (xyz float32 x 3, normal float32 x 3, rgb x 3, weight), and the counts [5] in the order of SURFACE_STATS."""
+    voxel = float(voxel)
+    good = lambda c: c in table and table[c][0] >= min_weight
+    D = lambda c: float(table[c][1]) / float(table[c][0])
+    step = lambda c, axis, by: tuple(c[k] + (by if k == axis else 0) for k in range(3))
+
+    def gradient(c):
+        g = []
+        for axis in range(3):
+            p, m = step(c, axis, 1), step(c, axis, -1)
+            if good(p) and good(m):
+                g.append((D(p) - D(m)) / 2.0)
+            elif good(p):
+                g.append(D(p) - D(c))
+            elif good(m):
+                g.append(D(c) - D(m))
+            else:
+                g.append(0.0)
+        return g
+
+    out, counts = [], [0] * len(SURFACE_STATS)
+    for a in sorted(table):
+        if not good(a):
+            counts[0] += 1
+            continue
+        for axis in range(3):
+            b = step(a, axis, 1)
+            if not good(b) or (table[a][1] >= 0) == (table[b][1] >= 0):
+                continue
+            t = D(a) / (D(a) - D(b))
+            ga, gb = gradient(a), gradient(b)
+            g = [(1.0 - t) * ga[k] + t * gb[k] for k in range(3)]
+            norm = math.sqrt((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2])
+            n = [np.float32(g[k] / norm) if norm > 0.0 else np.float32(0.0) for k in range(3)]
+            counts[4] += norm == 0.0
+            p = [np.float32((((float(a[k]) + 0.5) + t) if k == axis else (float(a[k]) + 0.5)) * voxel) for k in range(3)]
+            c = table[a] if t < 0.5 else table[b]
+            rgb = [(2 * c[2 + k] + c[0]) // (2 * c[0]) for k in range(3)]
+            out.append((p, n, rgb, min(table[a][0], table[b][0], 0x7fffffff)))
+            counts[1 + axis] += 1
+    return out, counts
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the kernels
+
+def inv_K_device(inv_K, device):
+    """The nine float64 entries of inv_K's 3x3 block as a device tensor (td_tsdf_samples reads them from device memory)."""
+    if torch.is_tensor(inv_K) and inv_K.is_cuda and inv_K.dtype == torch.float64 and tuple(inv_K.shape) == (9,):
+        return inv_K.contiguous()
+    return torch.from_numpy(cloud._inv_K9(inv_K.cpu().numpy() if torch.is_tensor(inv_K) else inv_K).copy()).to(device)
+
+
+def samples_hip(depth, color, poses, inv_K, T, voxel, mask=None, depth_scale=1.0, pose_scale=1.0, stride=1, border=0,
+                min_depth=cloud.DEFAULT_MIN_DEPTH, max_range=cloud.DEFAULT_MAX_RANGE, edge=0.0, stats=None):
+    """samples_numpy as one launch of td_tsdf_samples -> (key int64 [(4T+1) B H W], payload int64 [(4T+1) B H W]: the uint64's bits).
+    ``inv_K``: a float64 [9] device tensor (inv_K_device), or anything cloud accepts, which is uploaded;  ``mask``: a uint8 or bool
+    [B,H,W] device tensor or None;  ``stats``: an int64 [10] device tensor that the launch increments (SAMPLE_STATS), or None."""
+    native.require_device(depth, color, poses)
+    if depth.dtype != torch.float32 or depth.dim() != 3 or color.dtype != torch.uint8 or \
+            tuple(color.shape) != (depth.shape[0], 3) + tuple(depth.shape[1:]) or poses.dtype != torch.float64 or \
+            tuple(poses.shape) != (depth.shape[0], 3, 4):
+        raise ValueError("depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4]; got %s %s, %s %s, %s %s" % (
+            tuple(depth.shape), depth.dtype, tuple(color.shape), color.dtype, tuple(poses.shape), poses.dtype))
+    _check(T, voxel)
+    if int(stride) < 1 or int(border) < 0 or not edge >= 0:
+        raise ValueError("stride >= 1, border >= 0, edge >= 0")
+    if mask is not None:
+        native.require_device(mask)
+        if mask.dtype not in (torch.uint8, torch.bool) or mask.shape != depth.shape:
+            raise ValueError("mask: uint8 or bool %s, got %s %s" % (tuple(depth.shape), tuple(mask.shape), mask.dtype))
+        mask = mask.contiguous().view(torch.uint8)
+    if stats is not None:
+        stats = cloud._i64(stats, "stats", len(SAMPLE_STATS))
+    ik = inv_K_device(inv_K, depth.device)
+    B, H, W = depth.shape
+    n = (4 * int(T) + 1) * B * H * W
+    key = torch.empty(n, dtype=torch.int64, device=depth.device)
+    payload = torch.empty(n, dtype=torch.int64, device=depth.device)
+    if n == 0:                           # an empty tensor has no pointer to pass
+        return key, payload
+    native.call("td_tsdf_samples", depth.contiguous(), color.contiguous(), poses.contiguous(), ik, mask, B, H, W, int(T),
+                float(depth_scale), float(pose_scale), float(voxel), 1.0 / float(voxel), int(stride), int(border), float(min_depth),
+                float(max_range), float(edge), key, payload, stats)
+    return key, payload
+
+
+def surface_hip(keys, sums, voxel, min_weight=DEFAULT_MIN_WEIGHT, stats=None):
+    """surface_numpy as one launch of td_tsdf_surface -> (xyz float32 [V,3,3], normal float32 [V,3,3], rgb uint8 [V,3,3], weight int32
+    [V,3], mask bool [V,3]); only where mask is set do the other four hold anything.  ``stats``: an int64 [5] device tensor that the
+    launch increments (SURFACE_STATS), or None."""
+    keys = cloud._i64(keys, "keys")
+    V = keys.shape[0]
+    native.require_device(sums)
+    if sums.dtype != torch.int64 or tuple(sums.shape) != (V, 7):
+        raise ValueError("sums: int64 [%d,7], got %s %s" % (V, tuple(sums.shape), sums.dtype))
+    _check(1, voxel, min_weight)
+    if stats is not None:
+        stats = cloud._i64(stats, "stats", len(SURFACE_STATS))
+    dev = keys.device
+    xyz, normal = torch.empty(V, 3, 3, dtype=torch.float32, device=dev), torch.empty(V, 3, 3, dtype=torch.float32, device=dev)
+    rgb, weight = torch.empty(V, 3, 3, dtype=torch.uint8, device=dev), torch.empty(V, 3, dtype=torch.int32, device=dev)
+    mask = torch.empty(V, 3, dtype=torch.uint8, device=dev)
+    if V:
+        native.call("td_tsdf_surface", keys, sums.contiguous(), V, float(voxel), int(min_weight), xyz, normal, rgb, weight, mask, stats)
+    return xyz, normal, rgb, weight, mask.bool()
+
+
+class _TsdfMap:
+    """The running voxel map of signed distances, a sibling of cloud._DeviceMap: sorted unique keys and their rows, the counters."""
+
+    def __init__(self, device, inv_K, voxel, T, stride, border, min_depth, max_range, edge, depth_scale, pose_scale,
+                 pair_chunk=DEFAULT_PAIR_CHUNK, min_views=0, view_radius=cloud.DEFAULT_VIEW_RADIUS, view_tol=cloud.DEFAULT_VIEW_TOL, K=None):
+        _check(T, voxel)
+        cloud._check_view_params(min_views, view_radius, view_tol)
+        if int(pair_chunk) < 1:
+            raise ValueError("pair_chunk: at least 1, got %r" % (pair_chunk,))
+        self.min_views, self.radius = int(min_views), int(view_radius)          # the names SceneFuser's window plumbing reads
+        if self.min_views:
+            self.view_args = (inv_K, cloud._view_K9(K, inv_K), self.radius, float(view_tol), float(depth_scale), float(pose_scale), min_depth,
+                              max_range)
+        self.ik = inv_K_device(inv_K, device)
+        self.args = dict(T=int(T), voxel=float(voxel), depth_scale=float(depth_scale), pose_scale=float(pose_scale), stride=stride,
+                         border=border, min_depth=min_depth, max_range=max_range, edge=edge)
+        self.pair_chunk = int(pair_chunk)
+        self.keys = torch.zeros(0, dtype=torch.int64, device=device)
+        self.sums = torch.zeros(0, 7, dtype=torch.int64, device=device)
+        self.counts = torch.zeros(len(SAMPLE_STATS), dtype=torch.int64, device=device)
+
+    def add(self, depth, color, poses, window=None, votes=False, mask=None):
+        """One batch of centre frames (_DeviceMap.add's signature): its pairs, ``pair_chunk`` at a time, through cloud.table_hip into
+        the map (cloud.merge_hip).  The sums are integers, so the cut changes nothing.  With the filter on, ``window`` = (depth
+        [n,H,W], poses [n,3,4], centres, bounds) as in _DeviceMap.add: the votes of cloud.views_hip, compared with min_views, become
+        the batch's mask (and ``mask``, if given, is and-ed in).  ``votes`` is accepted and ignored: nothing is returned."""
+        if self.min_views:
+            keep = cloud.views_hip(window[0], window[1], *self.view_args, centres=window[2], bounds=window[3]) >= self.min_views
+            mask = keep if mask is None else keep & (mask != 0)
+        key, payload = samples_hip(depth, color, poses, self.ik, mask=mask, stats=self.counts, **self.args)
+        for at in range(0, key.shape[0], self.pair_chunk):
+            self.keys, self.sums = cloud.merge_hip(self.keys, self.sums, *cloud.table_hip(key[at:at + self.pair_chunk],
+                                                                                          payload[at:at + self.pair_chunk]))
+
+    def surface(self, voxel, min_weight):
+        counts = torch.zeros(len(SURFACE_STATS), dtype=torch.int64, device=self.keys.device)
+        xyz, normal, rgb, weight, hit = surface_hip(self.keys, self.sums, voxel, min_weight, stats=counts)
+        out = (xyz[hit], normal[hit], rgb[hit], weight[hit])
+        return Surface(*out, _stats(self.counts.cpu().numpy(), self.keys.shape[0], counts.cpu().numpy(), out[0].shape[0]))
+
+
+def fuse_tsdf_hip(depth, color, poses, inv_K, voxel=cloud.DEFAULT_VOXEL, trunc_voxels=DEFAULT_TRUNC_VOXELS,
+                  min_weight=DEFAULT_MIN_WEIGHT, batch_size=None, stride=1, border=0, min_depth=cloud.DEFAULT_MIN_DEPTH,
+                  max_range=cloud.DEFAULT_MAX_RANGE, edge=0.0, depth_scale=1.0, pose_scale=1.0, mask=None, min_views=0,
+                  view_radius=cloud.DEFAULT_VIEW_RADIUS, view_tol=cloud.DEFAULT_VIEW_TOL, K=None, pair_chunk=DEFAULT_PAIR_CHUNK, debug=None):
+    """fuse_tsdf_numpy on the device, ``batch_size`` frames at a time (default: all at once) and ``pair_chunk`` pairs of a batch at a
+    time -> Surface of device tensors.  With ``min_views`` > 0 the votes of cloud.views_hip (all frames as the window; td_cloud_views
+    is untouched) become the batch's mask."""
+    cloud._check_params(voxel, stride, border, min_depth, max_range, edge)
+    cloud._check_view_params(min_views, view_radius, view_tol)
+    _check(trunc_voxels, voxel, min_weight)
+    native.require_device(depth, color, poses)
+    n = depth.shape[0]
+    step = n if batch_size is None else int(batch_size)
+    if step < 1 and n:
+        raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
+    vmap = _TsdfMap(depth.device, inv_K, voxel, trunc_voxels, stride, border, min_depth, max_range, edge, depth_scale, pose_scale, pair_chunk,
+                    min_views, view_radius, view_tol, K)
+    for at in range(0, n, max(step, 1)):
+        end = min(at + step, n)
+        window = (depth, poses, (at, end), (0, n)) if vmap.min_views else None
+        vmap.add(depth[at:end], color[at:end], poses[at:end], window, mask=None if mask is None else mask[at:end])
+    if debug is not None:
+        debug["keys"], debug["sums"] = vmap.keys, vmap.sums
+    return vmap.surface(voxel, min_weight)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+
+class TsdfFuser:
+    """fuse(dataset, poses=None, frames=None) -> Surface.
+
+    The depth maps and the poses come from a cloud.SceneFuser held inside (its DepthPredictor, its pose chain, its frame upload):
+    ``model``, ``height``, ``width``, ``device``, ``batch_size``, ``precision``, ``post_process``, ``voxel``, ``stride``, ``border``,
+    ``min_depth``, ``max_range``, ``edge``, ``depth_scale``, ``pose_scale`` mean what they mean there.
+    trunc_voxels   the band T on either side of a pixel's surface, in voxels (1 ... 8); UNTUNED starting value
+    min_weight     a voxel takes part in the surface when at least this many samples fell into it; UNTUNED starting value
+    min_views, view_radius, view_tol   SceneFuser's multi-view filter, composed through the per-pixel mask: a pixel with fewer than
+                   min_views votes (cloud.views_numpy / views_hip) emits no sample.  On the device the frames go through
+                   SceneFuser's own sliding window (SceneFuser._fuse_filtered): at most batch_size + 2 view_radius depth maps are held.
+    pair_chunk     a batch makes B H W (4 trunc_voxels + 1) pairs (19 M at 12 x 192 x 640, T = 3); they are sorted and summed this
+                   many at a time.  The result does not depend on it, nor on batch_size.
+    device 'cuda[:i]': per batch DepthPredictor, samples_hip, then cloud's unchanged sort / heads / cumsum / reduce / merge; one
+    surface_hip at the end.  'cpu': the host statements.
+    """
+
+    def __init__(self, model, height, width, device, voxel=cloud.DEFAULT_VOXEL, trunc_voxels=DEFAULT_TRUNC_VOXELS,
+                 min_weight=DEFAULT_MIN_WEIGHT, batch_size=12, precision="fp32", stride=1, border=0, min_depth=cloud.DEFAULT_MIN_DEPTH,
+                 max_range=cloud.DEFAULT_MAX_RANGE, edge=cloud.DEFAULT_EDGE, depth_scale=1.0, pose_scale=1.0, post_process=False,
+                 min_views=0, view_radius=cloud.DEFAULT_VIEW_RADIUS, view_tol=cloud.DEFAULT_VIEW_TOL, pair_chunk=DEFAULT_PAIR_CHUNK):
+        _check(trunc_voxels, voxel, min_weight)
+        if int(pair_chunk) < 1:
+            raise ValueError("pair_chunk: at least 1, got %r" % (pair_chunk,))
+        # the scene fuser checks the shared parameters and owns the predictor and the pose chain; its own filter stays off
+        self.scene = cloud.SceneFuser(model, height, width, device, voxel=voxel, batch_size=batch_size, precision=precision, stride=stride,
+                                      border=border, min_depth=min_depth, max_range=max_range, edge=edge, depth_scale=depth_scale,
+                                      pose_scale=pose_scale, post_process=post_process)
+        cloud._check_view_params(min_views, view_radius, view_tol)
+        self.device, self.on_hip, self.batch_size = self.scene.device, self.scene.on_hip, self.scene.batch_size
+        self.voxel, self.T, self.min_weight, self.pair_chunk = float(voxel), int(trunc_voxels), int(min_weight), int(pair_chunk)
+        self.params = dict(self.scene.params)
+        self.views = dict(min_views=int(min_views), view_radius=int(view_radius), view_tol=float(view_tol))
+        self.poses = None                  # float64 [n+1,3,4] on the host: the poses of the last fuse()
+
+    def fuse(self, dataset, poses=None, frames=None, debug=None):
+        """``poses``, ``frames``: as SceneFuser.fuse.  ``debug``: a dict that receives the "depth" maps [m,H,W] and the "poses"
+        [n+1,3,4] that were fused."""
+        host_frames = cloud.odometry.dataset_frames_u8(dataset)
+        m = host_frames.shape[0]
+        first, last = (0, m) if frames is None else (int(frames[0]), int(frames[1]))
+        if not 0 <= first < last <= m:
+            raise ValueError("frames: 0 <= first < last <= %d, got %r" % (m, frames))
+        radius, min_views = self.views["view_radius"], self.views["min_views"]
+        if min_views and last - first < 2 * radius + 1:
+            raise ValueError("view_radius %d needs %d frames to fuse, got %d" % (radius, 2 * radius + 1, last - first))
+        inv_K = cloud.dataset_inv_K(dataset)
+        K = cloud.dataset_K(dataset)
+        resident = host_frames.to(self.device)
+        all_poses = self.scene._poses(dataset, resident, poses)
+        self.poses = all_poses.cpu().numpy() if torch.is_tensor(all_poses) else np.array(all_poses)
+        depths = []
+        with torch.no_grad():
+            if self.on_hip:
+                vmap = _TsdfMap(self.device, inv_K, self.voxel, self.T, pair_chunk=self.pair_chunk, K=K, **self.params, **self.views)
+            if self.on_hip and min_views:          # SceneFuser's sliding window, handing every ready batch of centres to vmap.add
+                self.scene._fuse_filtered(vmap, resident, all_poses, first, last, None if debug is None else depths, False)
+            else:
+                for at in range(first, last, self.batch_size):
+                    color = resident[at:min(at + self.batch_size, last)]
+                    depth = self.scene._predict(color)
+                    if self.on_hip:
+                        vmap.add(depth, color, all_poses[at:at + color.shape[0]])
+                    if debug is not None or not self.on_hip:
+                        depths.append(depth)
+            depths = torch.cat(depths) if depths else None
+            if self.on_hip:
+                surface = vmap.surface(self.voxel, self.min_weight)
+            else:
+                surface = fuse_tsdf_numpy(depths.numpy(), host_frames[first:last].numpy(), all_poses[first:last], inv_K, self.voxel, self.T,
+                                          self.min_weight, K=K, **self.params, **self.views)
+        if debug is not None:
+            debug["depth"], debug["poses"] = depths, all_poses
+        return surface
