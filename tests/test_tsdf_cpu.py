@@ -402,3 +402,59 @@ def test_device_entry_points_refuse_host_tensors():
         tsdf.surface_hip(torch.zeros(4, dtype=torch.int64), torch.zeros(4, 7, dtype=torch.int64), 0.25)
     with pytest.raises(native.NativeLibraryError):
         tsdf.fuse_tsdf_hip(depth, color, poses, inv_K, 0.25)
+
+
+# ---- the checks the two fusers share -------------------------------------------------------------------------------------------------
+
+def test_shared_frame_and_row_checks(monkeypatch):
+    depth, color, poses, inv_K = U.scene(0, 2, 4, 6)
+    d, c, p = (torch.from_numpy(a) for a in (depth, color, poses))
+    # the host variant converts what numpy can convert and refuses a wrong shape
+    got = cloud._check_frames(depth.astype(np.float64), color.astype(np.int64), poses.astype(np.float32), device=False)
+    assert [a.dtype for a in got] == [np.float32, np.uint8, np.float64] and all(a.flags.c_contiguous for a in got)
+    for bad in ((depth[0], color, poses), (depth, color[:, :2], poses), (depth, color[:, :, :3], poses), (depth, color, poses[:1]),
+                (depth, color, poses[:, :, :3])):
+        with pytest.raises(ValueError):
+            cloud._check_frames(*bad, device=False)
+    # the device variant refuses a host tensor before it looks at anything else; the same for the rows
+    keys, sums = torch.zeros(4, dtype=torch.int64), torch.zeros(4, 7, dtype=torch.int64)
+    with pytest.raises(native.NativeLibraryError):
+        cloud._check_frames(d, c, p, device=True)
+    with pytest.raises(native.NativeLibraryError):
+        cloud._check_rows(keys, sums)
+    # every former copy raises through the one check: the call is seen, and its error is the caller's
+    seen = []
+    for name in ("_check_frames", "_check_rows"):
+        real = getattr(cloud, name)
+        monkeypatch.setattr(cloud, name, lambda *a, _real=real, _name=name, **k: (seen.append(_name), _real(*a, **k))[1])
+    for site, error in ((lambda: cloud.keys_numpy(depth, color[:, :2], poses, inv_K), ValueError),
+                        (lambda: tsdf.samples_numpy(depth, color[:, :2], poses, inv_K, 3, 0.25), ValueError),
+                        (lambda: cloud.keys_hip(d, c, p, inv_K), native.NativeLibraryError),
+                        (lambda: tsdf.samples_hip(d, c, p, inv_K, 3, 0.25), native.NativeLibraryError)):
+        with pytest.raises(error):
+            site()
+    assert seen == ["_check_frames"] * 4
+    for site in (lambda: cloud.finish_hip(keys, sums, 0.25), lambda: cloud.merge_hip(keys, sums, keys, sums),
+                 lambda: tsdf.surface_hip(keys, sums, 0.25)):
+        with pytest.raises(native.NativeLibraryError):
+            site()
+    assert seen[4:] == ["_check_rows"] * 3
+    # with the device guard out of the way (there is no device here) the device variants refuse a wrong type and a wrong shape
+    monkeypatch.setattr(native, "require_device", lambda *tensors: None)
+    assert all(a is b for a, b in zip(cloud._check_frames(d, c, p, device=True), (d, c, p))) and cloud._check_rows(keys, sums) is keys
+    for bad in ((d.double(), c, p), (d, c.to(torch.int8), p), (d, c, p.float()), (d[0], c, p), (d, c[:, :2], p), (d, c, p[:1])):
+        with pytest.raises(ValueError):
+            cloud._check_frames(*bad, device=True)
+        with pytest.raises(ValueError):
+            cloud.keys_hip(*bad, inv_K)
+        with pytest.raises(ValueError):
+            tsdf.samples_hip(*bad, inv_K, 3, 0.25)
+    for bad in ((keys.int(), sums), (keys, sums.int()), (keys, sums[:3]), (keys, sums[:, :6]), (keys.reshape(2, 2), sums)):
+        with pytest.raises(ValueError):
+            cloud._check_rows(*bad)
+        with pytest.raises(ValueError):
+            cloud.finish_hip(*bad, 0.25)
+        with pytest.raises(ValueError):
+            cloud.merge_hip(keys, sums, *bad)
+        with pytest.raises(ValueError):
+            tsdf.surface_hip(*bad, 0.25)

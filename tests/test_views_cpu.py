@@ -259,3 +259,82 @@ def test_reconstruct_script_with_min_views(tmp_path):
     assert "invalid_views %d" % want.stats["invalid_views"] in run.stdout and "valid %d" % want.stats["valid"] in run.stdout
     tested = want.stats["valid"] + want.stats["invalid_views"]
     assert "consistency rate %.4f (%d of %d" % (want.stats["valid"] / max(tested, 1), want.stats["valid"], tested) in run.stdout
+
+
+# ---- 5. the sliding window's schedule and the driver's loop ----------------------------------------------------------------------
+
+def _clamped(i, first, last, radius):
+    return min(max(i - radius, first), last - 1 - 2 * radius)
+
+
+@pytest.mark.parametrize("radius", [1, 2])
+@pytest.mark.parametrize("batch_size", [1, 2, 3, 5, 12])
+@pytest.mark.parametrize("first", [0, 2])
+def test_window_schedule_over_all_small_cases(first, batch_size, radius):
+    for n in range(2 * radius + 1, 13):
+        last = first + n
+        predicted, centres, w0 = [], [], first
+        for at, end, ready, keep in cloud.window_schedule(first, last, batch_size, radius):
+            predicted += list(range(at, end))
+            assert 0 < end - at <= batch_size and end - w0 <= batch_size + 2 * radius          # what is held while the batch is fused
+            for c0, c1 in ready:
+                assert 0 < c1 - c0 <= batch_size
+                for i in range(c0, c1):          # the centre's clamped window lies inside the held frames w0 ... end-1
+                    a = _clamped(i, first, last, radius)
+                    assert w0 <= a and a + 2 * radius < end, (n, i, w0, end)
+                centres += list(range(c0, c1))
+            assert w0 <= keep <= end and end - keep <= batch_size + 2 * radius          # what is held on to the next batch
+            w0 = keep
+        assert predicted == list(range(first, last)), n          # every frame once, in order
+        assert centres == list(range(first, last)), n            # every centre once, ascending; none is left after the last batch
+
+
+class _RecordingSink:
+    def __init__(self, min_views, radius):
+        self.min_views, self.radius, self.calls = min_views, radius, []
+
+    def add(self, depth, color, poses, window=None):
+        self.calls.append((depth, color, poses, window))
+
+
+def _driver_inputs():
+    """7 frames of 4 x 6 whose pixels are the frame's number; the predictor in the driver's place answers 1 + number / 8 everywhere."""
+    color = torch.arange(7, dtype=torch.uint8).reshape(7, 1, 1, 1).expand(7, 3, 4, 6).contiguous()
+    poses = torch.arange(7 * 12, dtype=torch.float64).reshape(7, 3, 4)
+    predict = lambda c: 1.0 + c[:, 0].to(torch.float32) / 8.0
+    return color, poses, predict
+
+
+@pytest.mark.parametrize("first,last", [(0, 7), (2, 7)])
+def test_driver_loop_without_the_filter_hands_on_the_batches(first, last):
+    color, poses, predict = _driver_inputs()
+    sink, depths = _RecordingSink(0, 1), []
+    cloud.feed_frames(predict, sink, color, poses, first, last, 3, False, depths)
+    starts = list(range(first, last, 3))
+    assert len(sink.calls) == len(starts) == len(depths)
+    for at, (d, c, p, window), kept in zip(starts, sink.calls, depths):
+        end = min(at + 3, last)
+        assert window is None and torch.equal(d, predict(color[at:end])) and d.shape == (end - at, 4, 6) and kept is d
+        assert torch.equal(c, color[at:end]) and torch.equal(p, poses[at:end])
+
+
+@pytest.mark.parametrize("first,last", [(0, 7), (2, 7)])
+def test_driver_loop_with_the_filter_hands_on_centres_and_their_windows(first, last):
+    color, poses, predict = _driver_inputs()
+    radius, value = 1, lambda i: 1.0 + i / 8.0
+    sink, depths = _RecordingSink(1, radius), []
+    cloud.feed_frames(predict, sink, color, poses, first, last, 3, True, depths)
+    assert torch.equal(torch.cat(depths), predict(color[first:last]))          # every frame predicted once, in order
+    seen = []
+    for d, c, p, (held, held_poses, (c0, c1), (lo, hi)) in sink.calls:
+        frames = [int(round((float(v) - 1.0) * 8.0)) for v in held[:, 0, 0]]          # the frames the window holds, by their constants
+        assert frames == list(range(frames[0], frames[0] + len(frames))) and (lo, hi) == (0, len(frames))
+        assert torch.equal(held, torch.stack([torch.full((4, 6), value(i)) for i in frames]))
+        assert torch.equal(held_poses, poses[frames[0]:frames[-1] + 1])
+        centres = frames[c0:c1]
+        assert 0 < len(centres) <= 3 and torch.equal(d, held[c0:c1])
+        assert torch.equal(c, color[centres[0]:centres[-1] + 1]) and torch.equal(p, poses[centres[0]:centres[-1] + 1])
+        for local, i in zip(range(c0, c1), centres):          # the kernel's clamp inside the bounds picks the centre's true neighbours
+            assert frames[_clamped(local, lo, hi, radius)] == _clamped(i, first, last, radius)
+        seen += centres
+    assert seen == list(range(first, last))

@@ -17,7 +17,7 @@ Three layers, as in odometry.py:
     element-wise in the kernel's operation order: no ``@`` and no einsum, which BLAS may fuse;
   * ``keys_hip``, ``views_hip``, ``heads_hip``, ``reduce_hip``, ``finish_hip``, ``merge_hip`` (and ``table_hip`` / ``fuse_hip``, which
     chain them): device tensors only, a CPU tensor is an error; the kernels themselves never synchronise;
-  * ``SceneFuser``: frames of a dataset -> DepthPredictor + OdometryEvaluator.relative_poses / trajectory_hip -> the cloud.
+  * ``SequenceDriver`` (frames -> DepthPredictor + OdometryEvaluator.relative_poses / trajectory_hip -> a sink) and ``SceneFuser`` on it.
 
 The exact arithmetic (float64; every product and sum rounded on its own; pixel (u, v) at integer coordinates like the reference's
 Backproject, no half-pixel offset):
@@ -141,6 +141,22 @@ def _check_view_params(min_views, view_radius, view_tol):
         raise ValueError("min_views: 0 ... 2 view_radius = %d (a frame has that many neighbours), got %r" % (2 * int(view_radius), min_views))
 
 
+def _check_frames(depth, color, poses, device):
+    """depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4] -> the three, contiguous.  ``device``: tensors on a HIP device
+    of exactly those types (a CPU tensor is native.require_device's error); else anything numpy converts to them."""
+    kinds = (torch.float32, torch.uint8, torch.float64) if device else (np.float32, np.uint8, np.float64)
+    if device:
+        native.require_device(depth, color, poses)
+        t = [x.contiguous() for x in (depth, color, poses)]
+    else:
+        t = [np.ascontiguousarray(x, dtype=kind) for x, kind in zip((depth, color, poses), kinds)]
+    d, c, p = (tuple(x.shape) for x in t)
+    if [x.dtype for x in t] != list(kinds) or len(d) != 3 or c != (d[0], 3) + d[1:] or p != (d[0], 3, 4):
+        raise ValueError("depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4]; got " +
+                         ", ".join("%s %s" % (tuple(x.shape), x.dtype) for x in t))
+    return t
+
+
 def _inv_K9(inv_K, name="inv_K"):
     m = np.asarray(inv_K, dtype=np.float64)
     if m.shape in ((3, 3), (4, 4)):
@@ -220,11 +236,7 @@ def keys_numpy(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_
                min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=0.0):
     """depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4] -> (key int64 [B H W], payload uint64 [B H W], counts
     int64 [6] in the order of CAUSES).  The statement td_cloud_keys is tested against, operation for operation."""
-    d = np.ascontiguousarray(depth, dtype=np.float32)
-    c = np.ascontiguousarray(color, dtype=np.uint8)
-    P = np.ascontiguousarray(poses, dtype=np.float64)
-    if d.ndim != 3 or c.shape != (d.shape[0], 3) + d.shape[1:] or P.shape != (d.shape[0], 3, 4):
-        raise ValueError("depth [B,H,W], color [B,3,H,W], poses [B,3,4]; got %s, %s, %s" % (d.shape, c.shape, P.shape))
+    d, c, P = _check_frames(depth, color, poses, device=False)
     m = _inv_K9(inv_K)
     B, H, W = d.shape
     stride, border = int(stride), int(border)
@@ -439,16 +451,20 @@ def _i64(t, name, n=None):
     return t.contiguous()
 
 
+def _check_rows(keys, sums):
+    """A voxel list on the device: keys int64 [V], sums int64 [V,7] -> the keys, contiguous."""
+    keys = _i64(keys, "keys")
+    native.require_device(sums)
+    if sums.dtype != torch.int64 or tuple(sums.shape) != (keys.shape[0], 7):
+        raise ValueError("sums: int64 [%d,7], got %s %s" % (keys.shape[0], tuple(sums.shape), sums.dtype))
+    return keys
+
+
 def keys_hip(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_voxel=1.0 / DEFAULT_VOXEL, stride=1, border=0,
              min_depth=DEFAULT_MIN_DEPTH, max_range=DEFAULT_MAX_RANGE, edge=0.0, stats=None):
     """keys_numpy as one launch of td_cloud_keys -> (key int64 [B H W], payload int64 [B H W]: the uint64's bits).  ``stats``: an int64
     [6] device tensor that the launch increments (the order of CAUSES), or None."""
-    native.require_device(depth, color, poses)
-    if depth.dtype != torch.float32 or depth.dim() != 3 or color.dtype != torch.uint8 or \
-            tuple(color.shape) != (depth.shape[0], 3) + tuple(depth.shape[1:]) or poses.dtype != torch.float64 or \
-            tuple(poses.shape) != (depth.shape[0], 3, 4):
-        raise ValueError("depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4]; got %s %s, %s %s, %s %s" % (
-            tuple(depth.shape), depth.dtype, tuple(color.shape), color.dtype, tuple(poses.shape), poses.dtype))
+    depth, color, poses = _check_frames(depth, color, poses, device=True)
     if int(stride) < 1 or int(border) < 0 or not inv_voxel > 0 or not edge >= 0:
         raise ValueError("stride >= 1, border >= 0, inv_voxel > 0, edge >= 0")
     if stats is not None:
@@ -459,7 +475,7 @@ def keys_hip(depth, color, poses, inv_K, depth_scale=1.0, pose_scale=1.0, inv_vo
     payload = torch.empty(B * H * W, dtype=torch.int64, device=depth.device)
     if B * H * W == 0:                   # an empty tensor has no pointer to pass
         return key, payload
-    native.call("td_cloud_keys", depth.contiguous(), color.contiguous(), poses.contiguous(), (ctypes.c_double * 9)(*m), B, H, W,
+    native.call("td_cloud_keys", depth, color, poses, (ctypes.c_double * 9)(*m), B, H, W,
                 float(depth_scale), float(pose_scale), float(inv_voxel), int(stride), int(border), float(min_depth), float(max_range),
                 float(edge), key, payload, stats)
     return key, payload
@@ -534,11 +550,8 @@ def reduce_hip(sorted_keys, seg, perm, src, V):
 
 def finish_hip(keys, sums, voxel, min_count=1):
     """finish_numpy as td_cloud_finish -> (xyz float32 [V,3], rgb uint8 [V,3], count int32 [V], keep uint8 [V])."""
-    keys = _i64(keys, "keys")
+    keys = _check_rows(keys, sums)
     V = keys.shape[0]
-    native.require_device(sums)
-    if sums.dtype != torch.int64 or tuple(sums.shape) != (V, 7):
-        raise ValueError("sums: int64 [%d,7], got %s %s" % (V, tuple(sums.shape), sums.dtype))
     if not (np.isfinite(voxel) and voxel > 0):
         raise ValueError("voxel: a positive size, got %r" % (voxel,))
     dev = keys.device
@@ -564,11 +577,7 @@ def table_hip(key, src):
 
 def merge_hip(keys_a, sums_a, keys_b, sums_b):
     """Two voxel lists (unique keys, [.,7] rows) -> their union, rows of equal keys added: concatenate, table_hip."""
-    keys_a, keys_b = _i64(keys_a, "keys_a"), _i64(keys_b, "keys_b")
-    native.require_device(sums_a, sums_b)
-    for k, s in ((keys_a, sums_a), (keys_b, sums_b)):
-        if s.dtype != torch.int64 or tuple(s.shape) != (k.shape[0], 7):
-            raise ValueError("sums: int64 [%d,7], got %s %s" % (k.shape[0], tuple(s.shape), s.dtype))
+    keys_a, keys_b = _check_rows(keys_a, sums_a), _check_rows(keys_b, sums_b)
     if keys_a.shape[0] == 0:
         return keys_b, sums_b
     if keys_b.shape[0] == 0:
@@ -576,32 +585,59 @@ def merge_hip(keys_a, sums_a, keys_b, sums_b):
     return table_hip(torch.cat([keys_a, keys_b]), torch.cat([sums_a, sums_b]))
 
 
-class _DeviceMap:
-    """The running voxel map: sorted unique keys and their rows, plus the pixel counters."""
+class VoxelMap:
+    """The running voxel map on the device: ``keys`` int64 [V] sorted and unique, their rows ``sums`` int64 [V,7], and ``counts``, the
+    int64 [n_counters] that the kernel which makes the map's pairs increments."""
 
-    def __init__(self, device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale, min_views=0,
-                 view_radius=DEFAULT_VIEW_RADIUS, view_tol=DEFAULT_VIEW_TOL, K=None):
-        _check_view_params(min_views, view_radius, view_tol)
-        self.args = (inv_K, float(depth_scale), float(pose_scale), 1.0 / float(voxel), stride, border, min_depth, max_range, edge)
+    def __init__(self, device, n_counters):
         self.keys = torch.zeros(0, dtype=torch.int64, device=device)
         self.sums = torch.zeros(0, 7, dtype=torch.int64, device=device)
-        self.counts = torch.zeros(6, dtype=torch.int64, device=device)
+        self.counts = torch.zeros(n_counters, dtype=torch.int64, device=device)
+
+    def merge(self, key, payload, pair_chunk=None):
+        """A batch of pairs into the map, ``pair_chunk`` at a time (default: all at once); the sums are integers: the cut changes nothing."""
+        step = max(key.shape[0], 1) if pair_chunk is None else pair_chunk
+        for at in range(0, key.shape[0], step):
+            self.keys, self.sums = merge_hip(self.keys, self.sums, *table_hip(key[at:at + step], payload[at:at + step]))
+
+
+class FrameMap(VoxelMap):
+    """A VoxelMap that frames are fused into, and what the sequence driver asks of a sink: ``add(depth, color, poses, window)`` for one
+    batch of centre frames, ``min_views`` and ``radius``.  With the filter on, ``window`` = (depth [n,H,W], poses [n,3,4], centres,
+    bounds): the frames the neighbours come from and where the batch and the sequence's ends lie in them; ``votes`` is views_hip on it."""
+
+    def __init__(self, device, n_counters, inv_K, depth_scale, pose_scale, min_depth, max_range, min_views=0,
+                 view_radius=DEFAULT_VIEW_RADIUS, view_tol=DEFAULT_VIEW_TOL, K=None):
+        super().__init__(device, n_counters)
+        _check_view_params(min_views, view_radius, view_tol)
         self.min_views, self.radius = int(min_views), int(view_radius)
         if self.min_views:
             self.view_args = (inv_K, _view_K9(K, inv_K), self.radius, float(view_tol), float(depth_scale), float(pose_scale), min_depth,
                               max_range)
-            self.view_counts = torch.zeros(2, dtype=torch.int64, device=device)
 
-    def add(self, depth, color, poses, window=None, votes=False):
-        """One batch of centre frames.  With the filter on, ``window`` = (depth [n,H,W], poses [n,3,4], centres, bounds): the frames
-        the batch's neighbours come from and where the batch and the sequence's ends lie in them -> the votes, if asked for."""
-        key, payload = keys_hip(depth, color, poses, *self.args, stats=self.counts)
-        out = None
+    def votes(self, window, **kw):
+        return views_hip(window[0], window[1], *self.view_args, centres=window[2], bounds=window[3], **kw)
+
+
+class _DeviceMap(FrameMap):
+    """The voxel-averaged cloud's map: keys_hip makes the pairs, the filter invalidates them in place.  ``want_votes``: keep the votes
+    of every batch in ``self.kept_votes``."""
+
+    def __init__(self, device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale, min_views=0,
+                 view_radius=DEFAULT_VIEW_RADIUS, view_tol=DEFAULT_VIEW_TOL, K=None, want_votes=False):
+        super().__init__(device, 6, inv_K, depth_scale, pose_scale, min_depth, max_range, min_views, view_radius, view_tol, K)
+        self.args = (inv_K, float(depth_scale), float(pose_scale), 1.0 / float(voxel), stride, border, min_depth, max_range, edge)
         if self.min_views:
-            out = views_hip(window[0], window[1], *self.view_args, centres=window[2], bounds=window[3], key=key, payload=payload,
-                            min_views=self.min_views, stats=self.view_counts, votes=votes)
-        self.keys, self.sums = merge_hip(self.keys, self.sums, *table_hip(key, payload))
-        return out
+            self.view_counts = torch.zeros(2, dtype=torch.int64, device=device)
+        self.want_votes, self.kept_votes = bool(want_votes), []
+
+    def add(self, depth, color, poses, window=None):
+        key, payload = keys_hip(depth, color, poses, *self.args, stats=self.counts)
+        if self.min_views:
+            votes = self.votes(window, key=key, payload=payload, min_views=self.min_views, stats=self.view_counts, votes=self.want_votes)
+            if self.want_votes:
+                self.kept_votes.append(votes)
+        self.merge(key, payload)
 
     def cloud(self, voxel, min_count):
         xyz, rgb, count, keep = finish_hip(self.keys, self.sums, voxel, min_count)
@@ -609,6 +645,14 @@ class _DeviceMap:
         out = (xyz[keep], rgb[keep], count[keep], self.keys[keep])
         dropped = int(self.view_counts[1].item()) if self.min_views else None
         return Cloud(*out, _stats(self.counts.cpu().numpy(), self.keys.shape[0], out[3].shape[0], dropped))
+
+
+def frame_batches(first, last, batch_size):
+    """The (at, end) of the batches of at most ``batch_size`` frames (None: one batch) that cover first ... last-1."""
+    step = last - first if batch_size is None else int(batch_size)
+    if step < 1 and last > first:
+        raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
+    return [(at, min(at + step, last)) for at in range(first, last, max(step, 1))]
 
 
 def fuse_hip(depth, color, poses, inv_K, voxel=DEFAULT_VOXEL, batch_size=None, stride=1, border=0, min_depth=DEFAULT_MIN_DEPTH,
@@ -619,18 +663,12 @@ def fuse_hip(depth, color, poses, inv_K, voxel=DEFAULT_VOXEL, batch_size=None, s
     unchanged table and merge; with 0 no td_cloud_views is launched."""
     _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
     native.require_device(depth, color, poses)
-    n = depth.shape[0]
-    step = n if batch_size is None else int(batch_size)
-    if step < 1 and n:
-        raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
     vmap = _DeviceMap(depth.device, inv_K, voxel, stride, border, min_depth, max_range, edge, depth_scale, pose_scale, min_views,
-                      view_radius, view_tol, K)
-    votes = []
-    for at in range(0, n, max(step, 1)):
-        window = (depth, poses, (at, min(at + step, n)), (0, n)) if vmap.min_views else None
-        votes.append(vmap.add(depth[at:at + step], color[at:at + step], poses[at:at + step], window, debug is not None))
-    if debug is not None and vmap.min_views:
-        debug["votes"] = torch.cat(votes)
+                      view_radius, view_tol, K, want_votes=debug is not None)
+    for at, end in frame_batches(0, len(depth), batch_size):          # all frames are the filter's window
+        vmap.add(depth[at:end], color[at:end], poses[at:end], (depth, poses, (at, end), (0, len(depth))) if vmap.min_views else None)
+    if vmap.kept_votes:
+        debug["votes"] = torch.cat(vmap.kept_votes)
     return vmap.cloud(voxel, min_count)
 
 
@@ -643,11 +681,112 @@ def dataset_K(dataset):
 
 def dataset_inv_K(dataset):
     """The float64 inverse of the 3x3 block of the dataset's inputs["K"] (pixels at the dataset's frame size)."""
-    K = np.asarray(dataset[0]["K"], dtype=np.float64)
-    return np.linalg.inv(K[:3, :3])
+    return np.linalg.inv(dataset_K(dataset))
 
 
-class SceneFuser:
+def window_schedule(first, last, batch_size, radius):
+    """The multi-view filter's sliding window over the frames first ... last-1 (at least 2 radius + 1), predicted ``batch_size`` at a
+    time: yields (at, end, ready, keep) per batch.  The frames at ... end-1 join the held window; then the centres of ``ready``, a
+    list of (c0, c1) ranges of at most batch_size frames, are fused: a centre is ready once the last frame of its clamped window
+    (views_numpy's a ... a + 2 radius) is held; afterwards the window drops the frames before ``keep``, which no later centre needs.
+    Every frame is predicted once, every centre fused once, in order; at most batch_size + 2 radius depth maps are ever held."""
+    start = lambda i: min(max(i - radius, first), last - 1 - 2 * radius)          # the first frame of centre i's clamped window
+    centre, keep = first, first
+    for at, end in frame_batches(first, last, batch_size):
+        done = centre
+        while done < last and start(done) + 2 * radius < end:
+            done += 1
+        ready, centre = frame_batches(centre, done, batch_size), done
+        if centre < last:
+            keep = start(centre)
+        yield at, end, ready, keep
+
+
+def feed_frames(predict, sink, color, poses, first, last, batch_size, windowed, depths=None):
+    """The sequence driver's loop.  ``predict``: uint8 frames [b,3,H,W] -> depth float32 [b,H,W];  ``color`` [n,3,H,W], ``poses``
+    [n,3,4]: every frame's, of which first ... last-1 are fused;  ``depths``: a list that receives every batch's depth maps.
+    ``windowed`` (the filter on the device path): window_schedule's batches; the depth maps of the frames w0 ... end-1 are held, and
+    their ends stand in for the ends of the fused range: a centre that is ready has its whole clamped window inside."""
+    if not windowed:
+        for at, end in frame_batches(first, last, batch_size):
+            depth = predict(color[at:end])
+            sink.add(depth, color[at:end], poses[at:end])
+            if depths is not None:
+                depths.append(depth)
+        return
+    window, w0 = None, first
+    for at, end, ready, keep in window_schedule(first, last, batch_size, sink.radius):
+        depth = predict(color[at:end])
+        if depths is not None:
+            depths.append(depth)
+        window = depth if window is None else torch.cat([window, depth])
+        for c0, c1 in ready:                                                # at most a batch of points at a time
+            sink.add(window[c0 - w0:c1 - w0], color[c0:c1], poses[c0:c1], (window, poses[w0:end], (c0 - w0, c1 - w0), (0, end - w0)))
+        window, w0 = window[keep - w0:], keep
+
+
+class HostFrames:
+    """The host path's sink: it keeps the batches for the numpy chain, which takes all frames at once (``arrays``: depth [m,H,W],
+    color [m,3,H,W], poses [m,3,4] of the fused frames)."""
+
+    def __init__(self, min_views=0, view_radius=DEFAULT_VIEW_RADIUS):
+        self.min_views, self.radius, self.batches = int(min_views), int(view_radius), []
+
+    def add(self, depth, color, poses, window=None):
+        self.batches.append((depth, color, poses))
+
+    def arrays(self):
+        return tuple(np.concatenate([np.asarray(b[k]) for b in self.batches]) for k in range(3))
+
+
+class SequenceDriver:
+    """What SceneFuser and tsdf.TsdfFuser share: frames of a dataset -> DepthPredictor (``predictor``) + the pose chain -> a sink.
+    ``run`` uploads the frames once, checks the ranges and feeds the sink: sink.add(depth, color, poses, window) per batch (a
+    FrameMap; HostFrames on the host path), sink.min_views and sink.radius for the multi-view filter, whose sliding window runs on
+    the device path only.  ``poses``: float64 [n+1,3,4] on the host, the poses of the last run."""
+
+    def __init__(self, model, height, width, device, batch_size=12, precision="fp32", post_process=False):
+        self.device = infer.check_precision(device, precision, batch_size)
+        self.on_hip = self.device.type == "cuda"
+        self.model, self.batch_size, self.precision = model, int(batch_size), precision
+        self.predictor = infer.DepthPredictor(model, height, width, self.device, precision=precision, post_process=post_process)
+        self.poses = None
+
+    def predict(self, color):
+        return self.predictor.predict(color.permute(0, 2, 3, 1).contiguous()).depth.contiguous()
+
+    def camera_poses(self, dataset, frames, poses):
+        """float64 [n+1,3,4] camera-to-world, on the device (a numpy array on the host path)."""
+        m = frames.shape[0]
+        if poses is not None:
+            p = np.ascontiguousarray(np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, dtype=np.float64))
+            if p.ndim != 3 or p.shape[0] != m or p.shape[1:] not in ((3, 4), (4, 4)):
+                raise ValueError("poses: [%d,3,4] camera-to-world for %d frames, got %s" % (m, m, p.shape))
+            p = np.ascontiguousarray(p[:, :3])
+            return torch.from_numpy(p).to(self.device) if self.on_hip else p
+        rel = odometry.OdometryEvaluator(self.model, self.device, self.batch_size, self.precision).relative_poses(dataset, frames=frames)
+        return odometry.trajectory_hip(rel) if self.on_hip else odometry.trajectory_numpy(rel.numpy())
+
+    def run(self, dataset, sink, poses=None, frames=None, debug=None):
+        """``poses``, ``frames``, ``debug``: SceneFuser.fuse's; the driver fills debug["depth"] and debug["poses"]."""
+        host_frames = odometry.dataset_frames_u8(dataset)
+        m = host_frames.shape[0]
+        first, last = (0, m) if frames is None else (int(frames[0]), int(frames[1]))
+        if not 0 <= first < last <= m:
+            raise ValueError("frames: 0 <= first < last <= %d, got %r" % (m, frames))
+        if sink.min_views and last - first < 2 * sink.radius + 1:
+            raise ValueError("view_radius %d needs %d frames to fuse, got %d" % (sink.radius, 2 * sink.radius + 1, last - first))
+        resident = host_frames.to(self.device)                                   # every frame: one upload, as bytes
+        all_poses = self.camera_poses(dataset, resident, poses)
+        self.poses = all_poses.cpu().numpy() if torch.is_tensor(all_poses) else np.array(all_poses)
+        depths = None if debug is None else []
+        with torch.no_grad():
+            feed_frames(self.predict, sink, resident, all_poses, first, last, self.batch_size, self.on_hip and sink.min_views > 0, depths)
+        if debug is not None:
+            debug["depth"], debug["poses"] = torch.cat(depths), all_poses
+
+
+class SceneFuser(SequenceDriver):
     """fuse(dataset, poses=None, frames=None) -> Cloud.
 
     model       a model of this build with a depth network and, for ``poses=None``, ``PoseEncoder`` / ``PoseDecoder``; it is never
@@ -682,58 +821,13 @@ class SceneFuser:
                  pose_scale=1.0, post_process=False, min_views=0, view_radius=DEFAULT_VIEW_RADIUS, view_tol=DEFAULT_VIEW_TOL):
         _check_params(voxel, stride, border, min_depth, max_range, edge, min_count)
         _check_view_params(min_views, view_radius, view_tol)
-        self.device = infer.check_precision(device, precision, batch_size)
-        self.on_hip = self.device.type == "cuda"
-        self.model = model
-        self.batch_size, self.precision = int(batch_size), precision
-        self.predictor = infer.DepthPredictor(model, height, width, self.device, precision=precision, post_process=post_process)
+        super().__init__(model, height, width, device, batch_size, precision, post_process)
         self.voxel, self.min_count = float(voxel), int(min_count)
         self.params = dict(stride=int(stride), border=int(border), min_depth=float(min_depth), max_range=float(max_range),
                            edge=float(edge), depth_scale=float(depth_scale), pose_scale=float(pose_scale))
         self.min_views = int(min_views)
-        self.poses = None                  # float64 [n+1,3,4] on the host: the poses of the last fuse()
         if self.min_views:                 # off: the parameters of the filter reach nothing
             self.params.update(min_views=self.min_views, view_radius=int(view_radius), view_tol=float(view_tol))
-
-    def _predict(self, color):
-        return self.predictor.predict(color.permute(0, 2, 3, 1).contiguous()).depth.contiguous()
-
-    def _fuse_filtered(self, vmap, resident, all_poses, first, last, depths, want_votes):
-        """The device path with the multi-view filter on.  ``window`` holds the depth maps of the frames w0 ... have-1; a centre is
-        fused once the last frame of its clamped window is among them, and the window then drops what no later centre needs.  The
-        ends of the window stand in for the ends of the fused range: a centre that is ready has its whole clamped window inside."""
-        r, step = vmap.radius, self.batch_size
-        start = lambda i: min(max(i - r, first), last - 1 - 2 * r)          # the first frame of centre i's clamped window
-        window, w0, centre, votes = None, first, first, []
-        for at in range(first, last, step):
-            depth = self._predict(resident[at:min(at + step, last)])
-            if depths is not None:
-                depths.append(depth)
-            window = depth if window is None else torch.cat([window, depth])
-            have = at + depth.shape[0]
-            ready = centre
-            while ready < last and start(ready) + 2 * r < have:
-                ready += 1
-            while centre < ready:                                           # at most a batch of points at a time
-                c1 = min(centre + step, ready)
-                votes.append(vmap.add(window[centre - w0:c1 - w0], resident[centre:c1], all_poses[centre:c1],
-                                      (window, all_poses[w0:have], (centre - w0, c1 - w0), (0, have - w0)), want_votes))
-                centre = c1
-            if centre < last:
-                window, w0 = window[start(centre) - w0:], start(centre)
-        return torch.cat(votes) if want_votes else None
-
-    def _poses(self, dataset, frames, poses):
-        """float64 [n+1,3,4] camera-to-world, on the device (a numpy array on the host path)."""
-        m = frames.shape[0]
-        if poses is not None:
-            p = np.ascontiguousarray(np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, dtype=np.float64))
-            if p.ndim != 3 or p.shape[0] != m or p.shape[1:] not in ((3, 4), (4, 4)):
-                raise ValueError("poses: [%d,3,4] camera-to-world for %d frames, got %s" % (m, m, p.shape))
-            p = np.ascontiguousarray(p[:, :3])
-            return torch.from_numpy(p).to(self.device) if self.on_hip else p
-        rel = odometry.OdometryEvaluator(self.model, self.device, self.batch_size, self.precision).relative_poses(dataset, frames=frames)
-        return odometry.trajectory_hip(rel) if self.on_hip else odometry.trajectory_numpy(rel.numpy())
 
     def fuse(self, dataset, poses=None, frames=None, debug=None):
         """``poses``: any [n+1,3,4] camera-to-world array (KITTI ground truth with the user's depth_scale); None: the model's own.
@@ -741,42 +835,17 @@ class SceneFuser:
         receives the "depth" maps [m,H,W] and the "poses" [n+1,3,4] that were fused and, with the multi-view filter on, the "votes"
         uint8 [m,H,W] of the pixels it tested (0 where a single-frame filter had dropped the pixel already).  The poses that were
         used stay in ``self.poses`` (float64 [n+1,3,4] on the host): what render.CloudRenderer needs to look at the cloud."""
-        host_frames = odometry.dataset_frames_u8(dataset)
-        m = host_frames.shape[0]
-        first, last = (0, m) if frames is None else (int(frames[0]), int(frames[1]))
-        if not 0 <= first < last <= m:
-            raise ValueError("frames: 0 <= first < last <= %d, got %r" % (m, frames))
-        if self.min_views and last - first < 2 * self.params["view_radius"] + 1:
-            raise ValueError("view_radius %d needs %d frames to fuse, got %d" % (
-                self.params["view_radius"], 2 * self.params["view_radius"] + 1, last - first))
         inv_K = dataset_inv_K(dataset)
         view_K = {"K": dataset_K(dataset)} if self.min_views else {}
-        resident = host_frames.to(self.device)                                   # every frame: one upload, as bytes
-        all_poses = self._poses(dataset, resident, poses)
-        self.poses = all_poses.cpu().numpy() if torch.is_tensor(all_poses) else np.array(all_poses)
-        depths, votes = [], {}
-        with torch.no_grad():
-            if self.on_hip:
-                vmap = _DeviceMap(self.device, inv_K, self.voxel, **self.params, **view_K)
-            if self.on_hip and self.min_views:
-                votes["votes"] = self._fuse_filtered(vmap, resident, all_poses, first, last, None if debug is None else depths,
-                                                     debug is not None)
-            else:
-                for at in range(first, last, self.batch_size):
-                    color = resident[at:min(at + self.batch_size, last)]
-                    depth = self._predict(color)
-                    if self.on_hip:
-                        vmap.add(depth, color, all_poses[at:at + color.shape[0]])
-                    if debug is not None or not self.on_hip:
-                        depths.append(depth)
-            if self.on_hip:
-                cloud = vmap.cloud(self.voxel, self.min_count)
-            else:
-                cloud = fuse_numpy(torch.cat(depths).numpy(), host_frames[first:last].numpy(), all_poses[first:last], inv_K, self.voxel,
-                                   min_count=self.min_count, debug=votes, **self.params, **view_K)
-                if "votes" in votes:
-                    votes["votes"] = torch.from_numpy(votes["votes"])
-        if debug is not None:
-            debug["depth"], debug["poses"] = torch.cat(depths), all_poses
-            debug.update(votes)
+        sink = _DeviceMap(self.device, inv_K, self.voxel, **self.params, **view_K, want_votes=debug is not None) if self.on_hip else \
+            HostFrames(self.min_views, self.params.get("view_radius", DEFAULT_VIEW_RADIUS))
+        self.run(dataset, sink, poses, frames, debug)
+        if self.on_hip:
+            if sink.kept_votes:
+                debug["votes"] = torch.cat(sink.kept_votes)
+            return sink.cloud(self.voxel, self.min_count)
+        votes = {}
+        cloud = fuse_numpy(*sink.arrays(), inv_K, self.voxel, min_count=self.min_count, debug=votes, **self.params, **view_K)
+        if debug is not None and "votes" in votes:
+            debug["votes"] = torch.from_numpy(votes["votes"])
         return cloud

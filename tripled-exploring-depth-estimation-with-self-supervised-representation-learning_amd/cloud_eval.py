@@ -406,16 +406,13 @@ class ScanFuser:
             keys, sums = cloud.voxel_table_numpy(key, payload)
             xyz, rgb, count, _ = cloud.finish_numpy(keys, sums, self.voxel)
             return cloud.Cloud(xyz, rgb, count, keys, self._stats(counts, len(keys)))
-        keys = torch.zeros(0, dtype=torch.int64, device=self.device)
-        sums = torch.zeros(0, 7, dtype=torch.int64, device=self.device)
-        counts = torch.zeros(5, dtype=torch.int64, device=self.device)
+        vmap = cloud.VoxelMap(self.device, len(SCAN_CAUSES))
         for at in range(0, len(scans), self.batch_size):
             points, offsets, part = batch(at, self.batch_size)
-            key, payload = scan_keys_hip(torch.from_numpy(points).to(self.device), torch.from_numpy(offsets).to(self.device), self.Tr,
-                                         torch.from_numpy(part).to(self.device), stats=counts, **self.params)
-            keys, sums = cloud.merge_hip(keys, sums, *cloud.table_hip(key, payload))
-        xyz, rgb, count, _ = cloud.finish_hip(keys, sums, self.voxel)
-        return cloud.Cloud(xyz, rgb, count, keys, self._stats(counts.cpu().numpy(), keys.shape[0]))
+            vmap.merge(*scan_keys_hip(torch.from_numpy(points).to(self.device), torch.from_numpy(offsets).to(self.device), self.Tr,
+                                      torch.from_numpy(part).to(self.device), stats=vmap.counts, **self.params))
+        xyz, rgb, count, _ = cloud.finish_hip(vmap.keys, vmap.sums, self.voxel)
+        return cloud.Cloud(xyz, rgb, count, vmap.keys, self._stats(vmap.counts.cpu().numpy(), vmap.keys.shape[0]))
 
     @staticmethod
     def _stats(counts, voxels):

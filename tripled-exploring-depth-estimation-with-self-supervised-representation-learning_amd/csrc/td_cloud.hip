@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "td_grid.h"
+#include "td_pixel.h"
 
 namespace td {
 
@@ -33,95 +34,44 @@ struct CloudKeyArgs {
   unsigned long long* stats;   // [6] or NULL: += valid, off-lattice, border, depth, edge, range
 };
 
-// A thread owns VEC consecutive columns of one row; VEC divides W, so the flat pixel index of chunk c is c * VEC and a wave's
-// loads and stores are contiguous.  The rows above and below are read with the same alignment; the left and right neighbours of
-// the run are two scalar loads that the neighbouring threads' lines already hold.
+// td_pixel.h's run of VEC columns per thread and its causes 1 ... 4; cause 5 here is a voxel out of the key's range.
 template <int VEC>
 __global__ __launch_bounds__(TD_THREADS) void cloud_keys_kernel(const CloudKeyArgs a) {
   __shared__ unsigned cnt[6];
-  if (a.stats) {
-    if (threadIdx.x < 6) cnt[threadIdx.x] = 0;
-    __syncthreads();
-  }
-  const int H = a.H, W = a.W;
-  const long long cpr = W / VEC;
-  const long long c = (long long)blockIdx.x * TD_THREADS + threadIdx.x;
+  if (a.stats) counters_begin<6>(cnt);
   unsigned local[6] = {0, 0, 0, 0, 0, 0};
-  if (c < (long long)a.B * H * cpr) {
-    const long long row = c / cpr;
-    const int x0 = (int)(c - row * cpr) * VEC;
-    const int b = (int)(row / H);
-    const int y = (int)(row - (long long)b * H);
-    const long long pix = c * VEC;
-    const long long plane = (long long)H * W;
-    float d[VEC], up[VEC], dn[VEC];
-    uint8_t cr[VEC], cg[VEC], cb[VEC];
-    load_run<VEC>(a.depth + pix, d);
-    const uint8_t* col = a.color + ((long long)b * 3 * H + y) * W + x0;
-    load_run<VEC>(col, cr);
-    load_run<VEC>(col + plane, cg);
-    load_run<VEC>(col + 2 * plane, cb);
-    const bool use_edge = a.edge > 0.f;
-    const bool has_up = y > 0, has_dn = y + 1 < H, has_l = x0 > 0, has_r = x0 + VEC < W;
-    float left = 0.f, right = 0.f;
-    if (use_edge) {
-      if (has_up) load_run<VEC>(a.depth + pix - W, up);
-      if (has_dn) load_run<VEC>(a.depth + pix + W, dn);
-      if (has_l) left = a.depth[pix - 1];
-      if (has_r) right = a.depth[pix + VEC];
-    }
+  PixelRun<VEC> r;
+  if (pixel_run_load<VEC>(a, nullptr, r)) {
     double P[12];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) P[k] = a.poses[(long long)b * 12 + k];
-    const double v = (double)y;
+    for (int k = 0; k < 12; ++k) P[k] = a.poses[(long long)r.b * 12 + k];
+    const double v = (double)r.y;
     long long key[VEC];
     unsigned long long pay[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const int x = x0 + j;
-      int cause = 0;
+      int cause = r.cause[j];
       long long kk = TD_KEY_INVALID;
       unsigned long long pp = 0;
-      const double ds = (double)d[j] * a.depth_scale;
-      if (x % a.stride != 0 || y % a.stride != 0) cause = 1;
-      else if (x < a.border || x >= W - a.border || y < a.border || y >= H - a.border) cause = 2;
-      else if (!isfinite(d[j]) || !(ds >= a.min_depth && ds <= a.max_range)) cause = 3;
-      else if (use_edge) {
-        bool bad = false;
-        if (has_up) bad = bad || edge_bad(d[j], up[j], a.edge);
-        if (has_dn) bad = bad || edge_bad(d[j], dn[j], a.edge);
-        if (j > 0) bad = bad || edge_bad(d[j], d[j > 0 ? j - 1 : 0], a.edge);
-        else if (has_l) bad = bad || edge_bad(d[j], left, a.edge);
-        if (j + 1 < VEC) bad = bad || edge_bad(d[j], d[j + 1 < VEC ? j + 1 : j], a.edge);
-        else if (has_r) bad = bad || edge_bad(d[j], right, a.edge);
-        if (bad) cause = 4;
-      }
       if (cause == 0) {
-        const double u = (double)x;
-        const double r0 = (a.ik[0] * u + a.ik[1] * v) + a.ik[2];
-        const double r1 = (a.ik[3] * u + a.ik[4] * v) + a.ik[5];
-        const double r2 = (a.ik[6] * u + a.ik[7] * v) + a.ik[8];
+        double r0, r1, r2;
+        pixel_ray(a.ik, (double)(r.x0 + j), v, r0, r1, r2);
+        const double ds = r.ds[j];
         const double px = ds * r0, py = ds * r1, pz = ds * r2;
         double wx, wy, wz;
         camera_to_world(P, a.pose_scale, px, py, pz, wx, wy, wz);
         kk = voxel_key(wx * a.inv_voxel, wy * a.inv_voxel, wz * a.inv_voxel, pp);
         if (kk == TD_KEY_INVALID) cause = 5;
-        else pp |= ((unsigned long long)cr[j] << 30) | ((unsigned long long)cg[j] << 38) | ((unsigned long long)cb[j] << 46);
+        else pp |= pixel_rgb(r, j);
       }
       key[j] = kk;
       pay[j] = pp;
       local[cause] += 1;
     }
-    store_run<VEC>(a.key + pix, key);
-    store_run<VEC>(a.payload + pix, pay);
+    store_run<VEC>(a.key + r.pix, key);
+    store_run<VEC>(a.payload + r.pix, pay);
   }
-  if (a.stats) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-      if (local[k]) atomicAdd(&cnt[k], local[k]);      // LDS
-    __syncthreads();
-    if (threadIdx.x < 6 && cnt[threadIdx.x]) atomicAdd(a.stats + threadIdx.x, (unsigned long long)cnt[threadIdx.x]);
-  }
+  if (a.stats) counters_end<6>(cnt, local, a.stats);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -289,18 +239,7 @@ extern "C" int td_cloud_keys(const float* depth, const uint8_t* color, const dou
   a.B = B; a.H = H; a.W = W; a.stride = stride; a.border = border;
   a.depth_scale = depth_scale; a.pose_scale = pose_scale; a.inv_voxel = inv_voxel; a.min_depth = min_depth; a.max_range = max_range;
   a.edge = edge; a.key = key; a.payload = payload; a.stats = reinterpret_cast<unsigned long long*>(stats);
-  // the widest run the row length and the four base pointers allow
-  int vec = 4;
-  while (vec > 1 && !(W % vec == 0 && td::aligned_to(depth, 4 * vec) && td::aligned_to(color, vec) && td::aligned_to(key, 8 * vec) &&
-                      td::aligned_to(payload, 8 * vec)))
-    vec >>= 1;
-  const dim3 grid(td::blocks_1d((long long)B * H * (W / vec))), block(TD_THREADS);
-  if (!grid.x) return TD_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  if (vec == 4) hipLaunchKernelGGL((td::cloud_keys_kernel<4>), grid, block, 0, s, a);
-  else if (vec == 2) hipLaunchKernelGGL((td::cloud_keys_kernel<2>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((td::cloud_keys_kernel<1>), grid, block, 0, s, a);
-  return td::record_launch_error(hipGetLastError(), "td_cloud_keys");
+  return td::launch_pixel_runs(td::cloud_keys_kernel<4>, td::cloud_keys_kernel<2>, td::cloud_keys_kernel<1>, a, nullptr, stream, "td_cloud_keys");
 }
 
 extern "C" int td_cloud_heads(const long long* keys, long long N, int* flags, td_stream_t stream) {

@@ -47,31 +47,6 @@ __device__ __forceinline__ void camera_to_world(const double* __restrict__ P, do
   wz = ((P[8] * x + P[9] * y) + P[10] * z) + scale * P[11];
 }
 
-// What the per-pixel kernels share (td_cloud_keys, td_tsdf_samples): a thread's run of columns as one access, and the flying-pixel test.
-
-// VEC consecutive elements as one access (the caller guarantees sizeof(T) * VEC alignment)
-template <int VEC, typename T>
-__device__ __forceinline__ void load_run(const T* __restrict__ p, T* out) {
-  struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
-  const Pack pk = *reinterpret_cast<const Pack*>(p);
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) out[j] = pk.v[j];
-}
-
-template <int VEC, typename T>
-__device__ __forceinline__ void store_run(T* __restrict__ p, const T* in) {
-  struct alignas(sizeof(T) * VEC) Pack { T v[VEC]; };
-  Pack pk;
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) pk.v[j] = in[j];
-  *reinterpret_cast<Pack*>(p) = pk;
-}
-
-// the flying-pixel test against one neighbour, float32 on the unscaled depths
-__device__ __forceinline__ bool edge_bad(float d, float nb, float edge) {
-  return !isfinite(nb) || fabsf(d - nb) > edge * fminf(d, nb);
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // A cloud sorted into a uniform grid of cells (cloud_eval.grid_hip): cell_key [C] ascending, cell_start [C+1], points in cell order.
 // With inv_cell = (1 - 2^-20) / tau two points within tau lie in cells at most one apart on every axis, so the 27 cells around a

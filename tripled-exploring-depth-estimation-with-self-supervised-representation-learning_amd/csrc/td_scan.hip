@@ -6,6 +6,7 @@
 #include <math.h>
 
 #include "td_grid.h"
+#include "td_pixel.h"
 
 namespace td {
 
@@ -40,10 +41,7 @@ __device__ __forceinline__ int scan_of(const long long* __restrict__ offsets, in
 template <bool VEC>
 __global__ __launch_bounds__(TD_THREADS) void scan_keys_kernel(const ScanKeyArgs a) {
   __shared__ unsigned cnt[5];
-  if (a.stats) {
-    if (threadIdx.x < 5) cnt[threadIdx.x] = 0;
-    __syncthreads();
-  }
+  if (a.stats) counters_begin<5>(cnt);
   const long long i = (long long)blockIdx.x * TD_THREADS + threadIdx.x;
   int cause = -1;
   if (i < a.n) {
@@ -94,8 +92,7 @@ __global__ __launch_bounds__(TD_THREADS) void scan_keys_kernel(const ScanKeyArgs
   }
   if (a.stats) {
     if (cause >= 0) atomicAdd(&cnt[cause], 1u);      // LDS
-    __syncthreads();
-    if (threadIdx.x < 5 && cnt[threadIdx.x]) atomicAdd(a.stats + threadIdx.x, (unsigned long long)cnt[threadIdx.x]);
+    counters_end<5>(cnt, a.stats);
   }
 }
 

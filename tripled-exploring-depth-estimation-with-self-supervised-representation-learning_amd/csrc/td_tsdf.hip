@@ -10,6 +10,7 @@
 #include <math.h>
 
 #include "td_grid.h"
+#include "td_pixel.h"
 
 #define TD_TSDF_ONE 1048576      // 2^20: the distance `trunc` as an integer
 
@@ -32,84 +33,38 @@ struct TsdfSampleArgs {
   unsigned long long* stats;   // [TD_TSDF_SAMPLE_STATS] or NULL
 };
 
-// td_cloud_keys' thread layout: VEC consecutive columns of one row per thread.  The validity rules are its causes 1 ... 4 in its order,
-// then the mask.  Output is slot-major: the VEC pairs of one slot are one store, and a wave's stores of a slot are contiguous.
+// td_pixel.h's run of VEC columns per thread and its causes 1 ... 5: what td_cloud_keys drops, then the mask.  Output is slot-major: the
+// VEC pairs of one slot are one store, and a wave's stores of a slot are contiguous.
 template <int VEC>
 __global__ __launch_bounds__(TD_THREADS) void tsdf_samples_kernel(const TsdfSampleArgs a) {
   __shared__ unsigned cnt[TD_TSDF_SAMPLE_STATS];
-  if (a.stats) {
-    if (threadIdx.x < TD_TSDF_SAMPLE_STATS) cnt[threadIdx.x] = 0;
-    __syncthreads();
-  }
-  const int H = a.H, W = a.W, T = a.T;
-  const long long cpr = W / VEC;
-  const long long c = (long long)blockIdx.x * TD_THREADS + threadIdx.x;
-  const long long npix = (long long)a.B * H * W;
+  if (a.stats) counters_begin<TD_TSDF_SAMPLE_STATS>(cnt);
+  const int T = a.T;
+  const long long npix = (long long)a.B * a.H * a.W;
   unsigned local[TD_TSDF_SAMPLE_STATS];
 #pragma unroll
   for (int k = 0; k < TD_TSDF_SAMPLE_STATS; ++k) local[k] = 0;
-  if (c < (long long)a.B * H * cpr) {
-    const long long row = c / cpr;
-    const int x0 = (int)(c - row * cpr) * VEC;
-    const int b = (int)(row / H);
-    const int y = (int)(row - (long long)b * H);
-    const long long pix = c * VEC;
-    const long long plane = (long long)H * W;
-    float d[VEC], up[VEC], dn[VEC];
-    uint8_t cr[VEC], cg[VEC], cb[VEC], mk[VEC];
-    load_run<VEC>(a.depth + pix, d);
-    const uint8_t* col = a.color + ((long long)b * 3 * H + y) * W + x0;
-    load_run<VEC>(col, cr);
-    load_run<VEC>(col + plane, cg);
-    load_run<VEC>(col + 2 * plane, cb);
-    if (a.mask) load_run<VEC>(a.mask + pix, mk);
-    const bool use_edge = a.edge > 0.f;
-    const bool has_up = y > 0, has_dn = y + 1 < H, has_l = x0 > 0, has_r = x0 + VEC < W;
-    float left = 0.f, right = 0.f;
-    if (use_edge) {
-      if (has_up) load_run<VEC>(a.depth + pix - W, up);
-      if (has_dn) load_run<VEC>(a.depth + pix + W, dn);
-      if (has_l) left = a.depth[pix - 1];
-      if (has_r) right = a.depth[pix + VEC];
-    }
+  PixelRun<VEC> r;
+  if (pixel_run_load<VEC>(a, a.mask, r)) {
+    const long long pix = r.pix;
     double P[12], ik[9];
 #pragma unroll
-    for (int k = 0; k < 12; ++k) P[k] = a.poses[(long long)b * 12 + k];
+    for (int k = 0; k < 12; ++k) P[k] = a.poses[(long long)r.b * 12 + k];
 #pragma unroll
     for (int k = 0; k < 9; ++k) ik[k] = a.ik[k];
-    const double v = (double)y;
+    const double v = (double)r.y;
     bool ok[VEC];
     double r0[VEC], r1[VEC], r2[VEC], pz[VEC];
     unsigned long long rgb[VEC];
     long long prev[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
-      const int x = x0 + j;
-      int cause = 0;
-      const double ds = (double)d[j] * a.depth_scale;
-      if (x % a.stride != 0 || y % a.stride != 0) cause = 1;
-      else if (x < a.border || x >= W - a.border || y < a.border || y >= H - a.border) cause = 2;
-      else if (!isfinite(d[j]) || !(ds >= a.min_depth && ds <= a.max_range)) cause = 3;
-      else if (use_edge) {
-        bool bad = false;
-        if (has_up) bad = bad || edge_bad(d[j], up[j], a.edge);
-        if (has_dn) bad = bad || edge_bad(d[j], dn[j], a.edge);
-        if (j > 0) bad = bad || edge_bad(d[j], d[j > 0 ? j - 1 : 0], a.edge);
-        else if (has_l) bad = bad || edge_bad(d[j], left, a.edge);
-        if (j + 1 < VEC) bad = bad || edge_bad(d[j], d[j + 1 < VEC ? j + 1 : j], a.edge);
-        else if (has_r) bad = bad || edge_bad(d[j], right, a.edge);
-        if (bad) cause = 4;
-      }
-      if (cause == 0 && a.mask && mk[j] == 0) cause = 5;
-      const double u = (double)x;
-      r0[j] = (ik[0] * u + ik[1] * v) + ik[2];
-      r1[j] = (ik[3] * u + ik[4] * v) + ik[5];
-      r2[j] = (ik[6] * u + ik[7] * v) + ik[8];
-      pz[j] = ds * r2[j];
-      ok[j] = cause == 0;
-      rgb[j] = ((unsigned long long)cr[j] << 30) | ((unsigned long long)cg[j] << 38) | ((unsigned long long)cb[j] << 46);
+      pixel_ray(ik, (double)(r.x0 + j), v, r0[j], r1[j], r2[j]);
+      pz[j] = r.ds[j] * r2[j];
+      ok[j] = r.cause[j] == 0;
+      rgb[j] = pixel_rgb(r, j);
       prev[j] = TD_KEY_INVALID;
-      local[cause] += 1;
+      local[r.cause[j]] += 1;
     }
     const double half = a.voxel * 0.5;
     const double trunc = (double)T * a.voxel;
@@ -159,14 +114,7 @@ __global__ __launch_bounds__(TD_THREADS) void tsdf_samples_kernel(const TsdfSamp
       store_run<VEC>(a.payload + at, pay);
     }
   }
-  if (a.stats) {
-#pragma unroll
-    for (int k = 0; k < TD_TSDF_SAMPLE_STATS; ++k)
-      if (local[k]) atomicAdd(&cnt[k], local[k]);      // LDS
-    __syncthreads();
-    if (threadIdx.x < TD_TSDF_SAMPLE_STATS && cnt[threadIdx.x])
-      atomicAdd(a.stats + threadIdx.x, (unsigned long long)cnt[threadIdx.x]);
-  }
+  if (a.stats) counters_end<TD_TSDF_SAMPLE_STATS>(cnt, local, a.stats);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -222,10 +170,7 @@ __global__ __launch_bounds__(TD_THREADS) void tsdf_surface_kernel(const long lon
                                                                   uint8_t* __restrict__ rgb, int* __restrict__ weight,
                                                                   uint8_t* __restrict__ mask, unsigned long long* __restrict__ stats) {
   __shared__ unsigned cnt[TD_TSDF_SURFACE_STATS];
-  if (stats) {
-    if (threadIdx.x < TD_TSDF_SURFACE_STATS) cnt[threadIdx.x] = 0;
-    __syncthreads();
-  }
+  if (stats) counters_begin<TD_TSDF_SURFACE_STATS>(cnt);
   const long long a = (long long)blockIdx.x * TD_THREADS + threadIdx.x;
   unsigned local[TD_TSDF_SURFACE_STATS] = {0, 0, 0, 0, 0};
   if (a < V) {
@@ -279,13 +224,7 @@ __global__ __launch_bounds__(TD_THREADS) void tsdf_surface_kernel(const long lon
       mask[a * 3 + axis] = cross ? 1 : 0;
     }
   }
-  if (stats) {
-#pragma unroll
-    for (int k = 0; k < TD_TSDF_SURFACE_STATS; ++k)
-      if (local[k]) atomicAdd(&cnt[k], local[k]);      // LDS
-    __syncthreads();
-    if (threadIdx.x < TD_TSDF_SURFACE_STATS && cnt[threadIdx.x]) atomicAdd(stats + threadIdx.x, (unsigned long long)cnt[threadIdx.x]);
-  }
+  if (stats) counters_end<TD_TSDF_SURFACE_STATS>(cnt, local, stats);
 }
 
 }  // namespace td
@@ -306,18 +245,9 @@ extern "C" int td_tsdf_samples(const float* depth, const uint8_t* color, const d
   a.depth_scale = depth_scale; a.pose_scale = pose_scale; a.voxel = voxel; a.inv_voxel = inv_voxel;
   a.min_depth = min_depth; a.max_range = max_range;
   a.edge = edge; a.key = key; a.payload = payload; a.stats = reinterpret_cast<unsigned long long*>(stats);
-  // the widest run the row length and the base pointers allow (a slot's plane starts B H W elements on: a multiple of the run)
-  int vec = 4;
-  while (vec > 1 && !(W % vec == 0 && td::aligned_to(depth, 4 * vec) && td::aligned_to(color, vec) && (!mask || td::aligned_to(mask, vec)) &&
-                      td::aligned_to(key, 8 * vec) && td::aligned_to(payload, 8 * vec)))
-    vec >>= 1;
-  const dim3 grid(td::blocks_1d((long long)B * H * (W / vec))), block(TD_THREADS);
-  if (!grid.x) return TD_ERR_UNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  if (vec == 4) hipLaunchKernelGGL((td::tsdf_samples_kernel<4>), grid, block, 0, s, a);
-  else if (vec == 2) hipLaunchKernelGGL((td::tsdf_samples_kernel<2>), grid, block, 0, s, a);
-  else hipLaunchKernelGGL((td::tsdf_samples_kernel<1>), grid, block, 0, s, a);
-  return td::record_launch_error(hipGetLastError(), "td_tsdf_samples");
+  // a slot's plane starts B H W elements on, a multiple of the run: the alignment of key and payload holds for every slot
+  return td::launch_pixel_runs(td::tsdf_samples_kernel<4>, td::tsdf_samples_kernel<2>, td::tsdf_samples_kernel<1>, a, mask, stream,
+                               "td_tsdf_samples");
 }
 
 extern "C" int td_tsdf_surface(const long long* keys, const long long* sums, long long V, double voxel, long long min_weight, float* xyz,

@@ -8,6 +8,7 @@
 #include <math.h>
 
 #include "td_grid.h"
+#include "td_pixel.h"
 
 namespace td {
 
@@ -35,10 +36,7 @@ __device__ __forceinline__ float view_tap(const float* __restrict__ frame, unsig
 
 __global__ __launch_bounds__(TD_THREADS) void cloud_views_kernel(const CloudViewArgs a) {
   __shared__ unsigned cnt[2];
-  if (a.stats) {
-    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
-    __syncthreads();
-  }
+  if (a.stats) counters_begin<2>(cnt);
   const int H = a.H, W = a.W;
   const unsigned plane = (unsigned)H * (unsigned)W;
   const unsigned ci = blockIdx.x / a.blocks_per_frame;                                    // wave-uniform: the centre's number
@@ -55,10 +53,8 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_views_kernel(const CloudView
       const double ds = (double)d * a.depth_scale;
       if (view_depth_ok(d, ds, a.min_depth, a.max_range)) {
         const unsigned y = pix / (unsigned)W, x = pix - y * (unsigned)W;
-        const double u = (double)x, v = (double)y;
-        const double r0 = (a.ik[0] * u + a.ik[1] * v) + a.ik[2];
-        const double r1 = (a.ik[3] * u + a.ik[4] * v) + a.ik[5];
-        const double r2 = (a.ik[6] * u + a.ik[7] * v) + a.ik[8];
+        double r0, r1, r2;
+        pixel_ray(a.ik, (double)x, (double)y, r0, r1, r2);
         const double px = ds * r0, py = ds * r1, pz = ds * r2;
         double wx, wy, wz;
         camera_to_world(a.poses + (long long)i * 12, a.pose_scale, px, py, pz, wx, wy, wz);
@@ -112,8 +108,7 @@ __global__ __launch_bounds__(TD_THREADS) void cloud_views_kernel(const CloudView
       if (bt) atomicAdd(&cnt[0], (unsigned)__popcll(bt));      // LDS
       if (bd) atomicAdd(&cnt[1], (unsigned)__popcll(bd));
     }
-    __syncthreads();
-    if (threadIdx.x < 2 && cnt[threadIdx.x]) atomicAdd(a.stats + threadIdx.x, (unsigned long long)cnt[threadIdx.x]);
+    counters_end<2>(cnt, a.stats);
   }
 }
 

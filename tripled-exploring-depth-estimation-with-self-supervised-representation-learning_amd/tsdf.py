@@ -58,13 +58,15 @@ on the fuser's device (numpy arrays on the host path);  stats: dict of Python in
 SURFACE_STATS, surface_points."""
 
 
-def _check(T, voxel, min_weight=1):
+def _check(T, voxel, min_weight=1, pair_chunk=1):
     if not 1 <= int(T) <= MAX_T:
         raise ValueError("trunc_voxels: 1 ... %d, got %r" % (MAX_T, T))
     if not (np.isfinite(voxel) and voxel > 0):
         raise ValueError("voxel: a positive size, got %r" % (voxel,))
     if int(min_weight) < 1:
         raise ValueError("min_weight: at least 1, got %r" % (min_weight,))
+    if int(pair_chunk) < 1:
+        raise ValueError("pair_chunk: at least 1, got %r" % (pair_chunk,))
 
 
 def row_sdf_sum(sums):
@@ -81,11 +83,7 @@ def samples_numpy(depth, color, poses, inv_K, T, voxel, mask=None, depth_scale=1
     """depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4], mask [B,H,W] (0 drops the pixel) or None -> (key int64
     [(4T+1) B H W], payload uint64 [(4T+1) B H W], slot-major, counts int64 [10] in the order of SAMPLE_STATS).  The statement
     td_tsdf_samples is tested against, operation for operation (the module's docstring)."""
-    d = np.ascontiguousarray(depth, dtype=np.float32)
-    c = np.ascontiguousarray(color, dtype=np.uint8)
-    P = np.ascontiguousarray(poses, dtype=np.float64)
-    if d.ndim != 3 or c.shape != (d.shape[0], 3) + d.shape[1:] or P.shape != (d.shape[0], 3, 4):
-        raise ValueError("depth [B,H,W], color [B,3,H,W], poses [B,3,4]; got %s, %s, %s" % (d.shape, c.shape, P.shape))
+    d, c, P = cloud._check_frames(depth, color, poses, device=False)
     _check(T, voxel)
     T = int(T)
     m = cloud._inv_K9(inv_K)
@@ -390,12 +388,7 @@ def samples_hip(depth, color, poses, inv_K, T, voxel, mask=None, depth_scale=1.0
     """samples_numpy as one launch of td_tsdf_samples -> (key int64 [(4T+1) B H W], payload int64 [(4T+1) B H W]: the uint64's bits).
     ``inv_K``: a float64 [9] device tensor (inv_K_device), or anything cloud accepts, which is uploaded;  ``mask``: a uint8 or bool
     [B,H,W] device tensor or None;  ``stats``: an int64 [10] device tensor that the launch increments (SAMPLE_STATS), or None."""
-    native.require_device(depth, color, poses)
-    if depth.dtype != torch.float32 or depth.dim() != 3 or color.dtype != torch.uint8 or \
-            tuple(color.shape) != (depth.shape[0], 3) + tuple(depth.shape[1:]) or poses.dtype != torch.float64 or \
-            tuple(poses.shape) != (depth.shape[0], 3, 4):
-        raise ValueError("depth float32 [B,H,W], color uint8 [B,3,H,W], poses float64 [B,3,4]; got %s %s, %s %s, %s %s" % (
-            tuple(depth.shape), depth.dtype, tuple(color.shape), color.dtype, tuple(poses.shape), poses.dtype))
+    depth, color, poses = cloud._check_frames(depth, color, poses, device=True)
     _check(T, voxel)
     if int(stride) < 1 or int(border) < 0 or not edge >= 0:
         raise ValueError("stride >= 1, border >= 0, edge >= 0")
@@ -413,7 +406,7 @@ def samples_hip(depth, color, poses, inv_K, T, voxel, mask=None, depth_scale=1.0
     payload = torch.empty(n, dtype=torch.int64, device=depth.device)
     if n == 0:                           # an empty tensor has no pointer to pass
         return key, payload
-    native.call("td_tsdf_samples", depth.contiguous(), color.contiguous(), poses.contiguous(), ik, mask, B, H, W, int(T),
+    native.call("td_tsdf_samples", depth, color, poses, ik, mask, B, H, W, int(T),
                 float(depth_scale), float(pose_scale), float(voxel), 1.0 / float(voxel), int(stride), int(border), float(min_depth),
                 float(max_range), float(edge), key, payload, stats)
     return key, payload
@@ -423,11 +416,8 @@ def surface_hip(keys, sums, voxel, min_weight=DEFAULT_MIN_WEIGHT, stats=None):
     """surface_numpy as one launch of td_tsdf_surface -> (xyz float32 [V,3,3], normal float32 [V,3,3], rgb uint8 [V,3,3], weight int32
     [V,3], mask bool [V,3]); only where mask is set do the other four hold anything.  ``stats``: an int64 [5] device tensor that the
     launch increments (SURFACE_STATS), or None."""
-    keys = cloud._i64(keys, "keys")
+    keys = cloud._check_rows(keys, sums)
     V = keys.shape[0]
-    native.require_device(sums)
-    if sums.dtype != torch.int64 or tuple(sums.shape) != (V, 7):
-        raise ValueError("sums: int64 [%d,7], got %s %s" % (V, tuple(sums.shape), sums.dtype))
     _check(1, voxel, min_weight)
     if stats is not None:
         stats = cloud._i64(stats, "stats", len(SURFACE_STATS))
@@ -440,39 +430,25 @@ def surface_hip(keys, sums, voxel, min_weight=DEFAULT_MIN_WEIGHT, stats=None):
     return xyz, normal, rgb, weight, mask.bool()
 
 
-class _TsdfMap:
-    """The running voxel map of signed distances, a sibling of cloud._DeviceMap: sorted unique keys and their rows, the counters."""
+class _TsdfMap(cloud.FrameMap):
+    """The voxel map of signed distances: samples_hip makes the pairs, the filter's votes become the batch's mask."""
 
     def __init__(self, device, inv_K, voxel, T, stride, border, min_depth, max_range, edge, depth_scale, pose_scale,
                  pair_chunk=DEFAULT_PAIR_CHUNK, min_views=0, view_radius=cloud.DEFAULT_VIEW_RADIUS, view_tol=cloud.DEFAULT_VIEW_TOL, K=None):
-        _check(T, voxel)
-        cloud._check_view_params(min_views, view_radius, view_tol)
-        if int(pair_chunk) < 1:
-            raise ValueError("pair_chunk: at least 1, got %r" % (pair_chunk,))
-        self.min_views, self.radius = int(min_views), int(view_radius)          # the names SceneFuser's window plumbing reads
-        if self.min_views:
-            self.view_args = (inv_K, cloud._view_K9(K, inv_K), self.radius, float(view_tol), float(depth_scale), float(pose_scale), min_depth,
-                              max_range)
+        _check(T, voxel, pair_chunk=pair_chunk)
+        super().__init__(device, len(SAMPLE_STATS), inv_K, depth_scale, pose_scale, min_depth, max_range, min_views, view_radius, view_tol, K)
         self.ik = inv_K_device(inv_K, device)
         self.args = dict(T=int(T), voxel=float(voxel), depth_scale=float(depth_scale), pose_scale=float(pose_scale), stride=stride,
                          border=border, min_depth=min_depth, max_range=max_range, edge=edge)
         self.pair_chunk = int(pair_chunk)
-        self.keys = torch.zeros(0, dtype=torch.int64, device=device)
-        self.sums = torch.zeros(0, 7, dtype=torch.int64, device=device)
-        self.counts = torch.zeros(len(SAMPLE_STATS), dtype=torch.int64, device=device)
 
-    def add(self, depth, color, poses, window=None, votes=False, mask=None):
-        """One batch of centre frames (_DeviceMap.add's signature): its pairs, ``pair_chunk`` at a time, through cloud.table_hip into
-        the map (cloud.merge_hip).  The sums are integers, so the cut changes nothing.  With the filter on, ``window`` = (depth
-        [n,H,W], poses [n,3,4], centres, bounds) as in _DeviceMap.add: the votes of cloud.views_hip, compared with min_views, become
-        the batch's mask (and ``mask``, if given, is and-ed in).  ``votes`` is accepted and ignored: nothing is returned."""
+    def add(self, depth, color, poses, window=None, mask=None):
+        """One batch of centre frames: its pairs, ``pair_chunk`` at a time, into the map.  With the filter on the votes, compared with
+        min_views, become the batch's mask (and ``mask``, if given, is and-ed in)."""
         if self.min_views:
-            keep = cloud.views_hip(window[0], window[1], *self.view_args, centres=window[2], bounds=window[3]) >= self.min_views
+            keep = self.votes(window) >= self.min_views
             mask = keep if mask is None else keep & (mask != 0)
-        key, payload = samples_hip(depth, color, poses, self.ik, mask=mask, stats=self.counts, **self.args)
-        for at in range(0, key.shape[0], self.pair_chunk):
-            self.keys, self.sums = cloud.merge_hip(self.keys, self.sums, *cloud.table_hip(key[at:at + self.pair_chunk],
-                                                                                          payload[at:at + self.pair_chunk]))
+        self.merge(*samples_hip(depth, color, poses, self.ik, mask=mask, stats=self.counts, **self.args), pair_chunk=self.pair_chunk)
 
     def surface(self, voxel, min_weight):
         counts = torch.zeros(len(SURFACE_STATS), dtype=torch.int64, device=self.keys.device)
@@ -492,16 +468,11 @@ def fuse_tsdf_hip(depth, color, poses, inv_K, voxel=cloud.DEFAULT_VOXEL, trunc_v
     cloud._check_view_params(min_views, view_radius, view_tol)
     _check(trunc_voxels, voxel, min_weight)
     native.require_device(depth, color, poses)
-    n = depth.shape[0]
-    step = n if batch_size is None else int(batch_size)
-    if step < 1 and n:
-        raise ValueError("batch_size: at least 1, got %r" % (batch_size,))
     vmap = _TsdfMap(depth.device, inv_K, voxel, trunc_voxels, stride, border, min_depth, max_range, edge, depth_scale, pose_scale, pair_chunk,
                     min_views, view_radius, view_tol, K)
-    for at in range(0, n, max(step, 1)):
-        end = min(at + step, n)
-        window = (depth, poses, (at, end), (0, n)) if vmap.min_views else None
-        vmap.add(depth[at:end], color[at:end], poses[at:end], window, mask=None if mask is None else mask[at:end])
+    for at, end in cloud.frame_batches(0, len(depth), batch_size):          # all frames are the filter's window
+        vmap.add(depth[at:end], color[at:end], poses[at:end], (depth, poses, (at, end), (0, len(depth))) if vmap.min_views else None,
+                 mask=None if mask is None else mask[at:end])
     if debug is not None:
         debug["keys"], debug["sums"] = vmap.keys, vmap.sums
     return vmap.surface(voxel, min_weight)
@@ -509,17 +480,17 @@ def fuse_tsdf_hip(depth, color, poses, inv_K, voxel=cloud.DEFAULT_VOXEL, trunc_v
 
 # ---------------------------------------------------------------------------------------------------------------------------
 
-class TsdfFuser:
+class TsdfFuser(cloud.SequenceDriver):
     """fuse(dataset, poses=None, frames=None) -> Surface.
 
-    The depth maps and the poses come from a cloud.SceneFuser held inside (its DepthPredictor, its pose chain, its frame upload):
-    ``model``, ``height``, ``width``, ``device``, ``batch_size``, ``precision``, ``post_process``, ``voxel``, ``stride``, ``border``,
+    The depth maps and the poses come from cloud.SequenceDriver, as SceneFuser's do (its DepthPredictor, its pose chain, its frame
+    upload): ``model``, ``height``, ``width``, ``device``, ``batch_size``, ``precision``, ``post_process``, ``voxel``, ``stride``, ``border``,
     ``min_depth``, ``max_range``, ``edge``, ``depth_scale``, ``pose_scale`` mean what they mean there.
     trunc_voxels   the band T on either side of a pixel's surface, in voxels (1 ... 8); UNTUNED starting value
     min_weight     a voxel takes part in the surface when at least this many samples fell into it; UNTUNED starting value
     min_views, view_radius, view_tol   SceneFuser's multi-view filter, composed through the per-pixel mask: a pixel with fewer than
                    min_views votes (cloud.views_numpy / views_hip) emits no sample.  On the device the frames go through
-                   SceneFuser's own sliding window (SceneFuser._fuse_filtered): at most batch_size + 2 view_radius depth maps are held.
+                   the driver's sliding window (cloud.window_schedule): at most batch_size + 2 view_radius depth maps are held.
     pair_chunk     a batch makes B H W (4 trunc_voxels + 1) pairs (19 M at 12 x 192 x 640, T = 3); they are sorted and summed this
                    many at a time.  The result does not depend on it, nor on batch_size.
     device 'cuda[:i]': per batch DepthPredictor, samples_hip, then cloud's unchanged sort / heads / cumsum / reduce / merge; one
@@ -530,56 +501,22 @@ class TsdfFuser:
                  min_weight=DEFAULT_MIN_WEIGHT, batch_size=12, precision="fp32", stride=1, border=0, min_depth=cloud.DEFAULT_MIN_DEPTH,
                  max_range=cloud.DEFAULT_MAX_RANGE, edge=cloud.DEFAULT_EDGE, depth_scale=1.0, pose_scale=1.0, post_process=False,
                  min_views=0, view_radius=cloud.DEFAULT_VIEW_RADIUS, view_tol=cloud.DEFAULT_VIEW_TOL, pair_chunk=DEFAULT_PAIR_CHUNK):
-        _check(trunc_voxels, voxel, min_weight)
-        if int(pair_chunk) < 1:
-            raise ValueError("pair_chunk: at least 1, got %r" % (pair_chunk,))
-        # the scene fuser checks the shared parameters and owns the predictor and the pose chain; its own filter stays off
-        self.scene = cloud.SceneFuser(model, height, width, device, voxel=voxel, batch_size=batch_size, precision=precision, stride=stride,
-                                      border=border, min_depth=min_depth, max_range=max_range, edge=edge, depth_scale=depth_scale,
-                                      pose_scale=pose_scale, post_process=post_process)
+        _check(trunc_voxels, voxel, min_weight, pair_chunk)
+        cloud._check_params(voxel, stride, border, min_depth, max_range, edge)
         cloud._check_view_params(min_views, view_radius, view_tol)
-        self.device, self.on_hip, self.batch_size = self.scene.device, self.scene.on_hip, self.scene.batch_size
+        super().__init__(model, height, width, device, batch_size, precision, post_process)
         self.voxel, self.T, self.min_weight, self.pair_chunk = float(voxel), int(trunc_voxels), int(min_weight), int(pair_chunk)
-        self.params = dict(self.scene.params)
+        self.params = dict(stride=int(stride), border=int(border), min_depth=float(min_depth), max_range=float(max_range),
+                           edge=float(edge), depth_scale=float(depth_scale), pose_scale=float(pose_scale))
         self.views = dict(min_views=int(min_views), view_radius=int(view_radius), view_tol=float(view_tol))
-        self.poses = None                  # float64 [n+1,3,4] on the host: the poses of the last fuse()
 
     def fuse(self, dataset, poses=None, frames=None, debug=None):
         """``poses``, ``frames``: as SceneFuser.fuse.  ``debug``: a dict that receives the "depth" maps [m,H,W] and the "poses"
         [n+1,3,4] that were fused."""
-        host_frames = cloud.odometry.dataset_frames_u8(dataset)
-        m = host_frames.shape[0]
-        first, last = (0, m) if frames is None else (int(frames[0]), int(frames[1]))
-        if not 0 <= first < last <= m:
-            raise ValueError("frames: 0 <= first < last <= %d, got %r" % (m, frames))
-        radius, min_views = self.views["view_radius"], self.views["min_views"]
-        if min_views and last - first < 2 * radius + 1:
-            raise ValueError("view_radius %d needs %d frames to fuse, got %d" % (radius, 2 * radius + 1, last - first))
-        inv_K = cloud.dataset_inv_K(dataset)
-        K = cloud.dataset_K(dataset)
-        resident = host_frames.to(self.device)
-        all_poses = self.scene._poses(dataset, resident, poses)
-        self.poses = all_poses.cpu().numpy() if torch.is_tensor(all_poses) else np.array(all_poses)
-        depths = []
-        with torch.no_grad():
-            if self.on_hip:
-                vmap = _TsdfMap(self.device, inv_K, self.voxel, self.T, pair_chunk=self.pair_chunk, K=K, **self.params, **self.views)
-            if self.on_hip and min_views:          # SceneFuser's sliding window, handing every ready batch of centres to vmap.add
-                self.scene._fuse_filtered(vmap, resident, all_poses, first, last, None if debug is None else depths, False)
-            else:
-                for at in range(first, last, self.batch_size):
-                    color = resident[at:min(at + self.batch_size, last)]
-                    depth = self.scene._predict(color)
-                    if self.on_hip:
-                        vmap.add(depth, color, all_poses[at:at + color.shape[0]])
-                    if debug is not None or not self.on_hip:
-                        depths.append(depth)
-            depths = torch.cat(depths) if depths else None
-            if self.on_hip:
-                surface = vmap.surface(self.voxel, self.min_weight)
-            else:
-                surface = fuse_tsdf_numpy(depths.numpy(), host_frames[first:last].numpy(), all_poses[first:last], inv_K, self.voxel, self.T,
-                                          self.min_weight, K=K, **self.params, **self.views)
-        if debug is not None:
-            debug["depth"], debug["poses"] = depths, all_poses
-        return surface
+        inv_K, K = cloud.dataset_inv_K(dataset), cloud.dataset_K(dataset)
+        sink = _TsdfMap(self.device, inv_K, self.voxel, self.T, pair_chunk=self.pair_chunk, K=K, **self.params, **self.views) if self.on_hip \
+            else cloud.HostFrames(self.views["min_views"], self.views["view_radius"])
+        self.run(dataset, sink, poses, frames, debug)
+        if self.on_hip:
+            return sink.surface(self.voxel, self.min_weight)
+        return fuse_tsdf_numpy(*sink.arrays(), inv_K, self.voxel, self.T, self.min_weight, K=K, **self.params, **self.views)
