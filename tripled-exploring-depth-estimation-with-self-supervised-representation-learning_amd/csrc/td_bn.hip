@@ -533,19 +533,26 @@ static BnRows shrink_partials(float* partials, int S, int G, int C, hipStream_t 
   return bn_shrink_partials_to(partials, S, G, C, BN_PRO_MAX_S, st);
 }
 
-// statistics (in the apply kernel's prologue) + apply, from partial sums; `partials` is reduced in place when S > BN_PRO_MAX_S
-template <typename T>
-static void launch_bn_finalize_apply(const void* x, const void* res, const float* gamma, const float* beta, float* rmean, float* rvar,
-                                     float momentum, float eps, int relu, long long Mg, int G, int C, float* partials, int S, void* y,
-                                     float* save_mean, float* save_invstd, hipStream_t st) {
-  const BnRows rows = shrink_partials(partials, S, G, C, st);
-  const int S2 = bn_splits(Mg, C, BN_STAT_BLOCKS, 4096), rps2 = bn_rows_per_split(Mg, S2);
-  const dim3 grid(C / 64, (unsigned)((Mg + rps2 - 1) / rps2), G);
-  const BnFinFwd fin = {partials, rows.n, rows.stride, S, G, eps, momentum, rmean, rvar, save_mean, save_invstd};
-  hipLaunchKernelGGL((bn_apply_kernel<T, true>), grid, dim3(BN_THREADS), 0, st, (const T*)x, (const T*)res, gamma, beta,
-                     (const float*)nullptr, (const float*)nullptr, Mg, C, rps2, relu, (T*)y, fin);
+// One pass over the Mg = M / G rows of each statistics group, cut into S ranges (bn_cut), S chosen for `target_blocks` workgroups
+// and at most `cap` ranges (bn_pass): every range is `rps` rows (a multiple of BN_RY), `rows` of them are not empty (<= S: trailing
+// empty ranges are not launched, and a statistics pass writes exactly `rows` partial rows), grid = (channel tiles, rows, G).
+struct BnPass {
+  long long Mg;
+  int rps, rows;
+  dim3 grid;
+};
+static inline BnPass bn_cut(long long M, int G, int C, int S) {
+  const long long Mg = M / G;
+  const int rps = bn_rows_per_split(Mg, S);
+  const int rows = (int)((Mg + rps - 1) / rps);
+  return {Mg, rps, rows, dim3(C / 64, rows, G)};
 }
-
+static inline BnPass bn_pass(long long M, int G, int C, int target_blocks, int cap) {
+  return bn_cut(M, G, C, bn_splits(M / G, C, target_blocks, cap));
+}
+// the statistics pass of td_bn_fwd / td_bn_bwd / the synchronised sums, and the apply and dx passes behind it
+static inline BnPass bn_sums_pass(long long M, int G, int C) { return bn_pass(M, G, C, BN_STAT_BLOCKS, 512); }
+static inline BnPass bn_rows_pass(long long M, int G, int C) { return bn_pass(M, G, C, BN_STAT_BLOCKS, 4096); }
 // row splits of a statistics pass whose partial rows a GEMM prologue finishes (td_conv1x1_fwd_bnrelu / td_conv1x1_dgrad_bnbwd: at
 // most 16 rows per block there): wide, short layers are cut into 16 ranges directly (no shrink launch); the others as every pass
 static inline int bn_stat_splits(long long Mg, int C) {
@@ -553,121 +560,85 @@ static inline int bn_stat_splits(long long Mg, int C) {
   if (S > 16 && (C / 64) * 16 >= 128) return bn_splits(Mg, C, (C / 64) * 16, 16);
   return S;
 }
-static inline int bn_stat_rows(long long Mg, int C) {
-  const int S = bn_stat_splits(Mg, C), rps = bn_rows_per_split(Mg, S);
-  return (int)((Mg + rps - 1) / rps);
-}
+static inline BnPass bn_stat_pass(long long M, int G, int C) { return bn_cut(M, G, C, bn_stat_splits(M / G, C)); }
 
+// the inputs of a backward pass; relu: 0 none, 1 mask from y, 2 mask recomputed from x (needs beta)
+struct BnBwdIn {
+  const void *dy, *x, *y;
+  const float *gamma, *beta, *mean, *invstd;
+  int relu;
+};
+
+// the statistics pass: mode 0 sums x and x^2 (`in` holds x alone), mode 1 the two backward sums; p.rows partial rows per group into ws
 template <typename T>
-static int run_bn_partials(int mode, const void* x, const void* dy, const void* y, const float* gamma, const float* beta, const float* mean,
-                           const float* invstd, int relu, long long M, int G, int C, float* ws, hipStream_t st) {
-  const long long Mg = M / G;
-  const int S = bn_stat_splits(Mg, C), rps = bn_rows_per_split(Mg, S);
-  const int S_eff = (int)((Mg + rps - 1) / rps);
+static void launch_bn_partials(int mode, const BnPass& p, const BnBwdIn& in, int C, float* ws, hipStream_t st) {
   if (mode == 0)
-    hipLaunchKernelGGL((bn_partials_kernel<T, 0>), dim3(C / 64, S_eff, G), dim3(BN_THREADS), 0, st, (const T*)x, (const T*)nullptr,
-                       (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, Mg, C,
-                       rps, 0, ws);
+    hipLaunchKernelGGL((bn_partials_kernel<T, 0>), p.grid, dim3(BN_THREADS), 0, st, (const T*)in.x, (const T*)nullptr, (const T*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, p.Mg, C, p.rps, 0, ws);
   else
-    hipLaunchKernelGGL((bn_partials_kernel<T, 1>), dim3(C / 64, S_eff, G), dim3(BN_THREADS), 0, st, (const T*)x, (const T*)dy,
-                       (const T*)y, mean, invstd, gamma, beta, Mg, C, rps, relu, ws);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+    hipLaunchKernelGGL((bn_partials_kernel<T, 1>), p.grid, dim3(BN_THREADS), 0, st, (const T*)in.x, (const T*)in.dy, (const T*)in.y,
+                       in.mean, in.invstd, in.gamma, in.beta, p.Mg, C, p.rps, in.relu, ws);
 }
 
-// dx (+ dgamma, dbeta) from backward partial sums formed elsewhere (a GEMM epilogue): shrink when needed, finish in bn_dx's prologue
+// statistics (in the apply kernel's prologue) + apply, from partial sums; `partials` is reduced in place when S > BN_PRO_MAX_S
 template <typename T>
-static int run_bn_dx_from_partials(const void* dy, const void* x, const void* y, const float* gamma, const float* beta, const float* mean,
-                                   const float* invstd, int relu, long long M, int G, int C, float* partials, int S, void* dx, void* dres,
-                                   float* dgamma, float* dbeta, hipStream_t st) {
-  const long long Mg = M / G;
+static void launch_bn_finalize_apply(const void* x, const void* res, const float* gamma, const float* beta, float* rmean, float* rvar,
+                                     float momentum, float eps, int relu, long long M, int G, int C, float* partials, int S, void* y,
+                                     float* save_mean, float* save_invstd, hipStream_t st) {
   const BnRows rows = shrink_partials(partials, S, G, C, st);
-  const int S2 = bn_splits(Mg, C, BN_STAT_BLOCKS, 4096), rps2 = bn_rows_per_split(Mg, S2);
-  const dim3 grid(C / 64, (unsigned)((Mg + rps2 - 1) / rps2), G);
+  const BnPass p = bn_rows_pass(M, G, C);
+  const BnFinFwd fin = {partials, rows.n, rows.stride, S, G, eps, momentum, rmean, rvar, save_mean, save_invstd};
+  hipLaunchKernelGGL((bn_apply_kernel<T, true>), p.grid, dim3(BN_THREADS), 0, st, (const T*)x, (const T*)res, gamma, beta,
+                     (const float*)nullptr, (const float*)nullptr, p.Mg, C, p.rps, relu, (T*)y, fin);
+}
+
+// dx (+ dgamma, dbeta) from S rows of backward partial sums (this file's pass or a GEMM epilogue): shrink when needed, finish in
+// bn_dx's prologue
+template <typename T>
+static void launch_bn_shrink_dx(const BnBwdIn& in, long long M, int G, int C, float* partials, int S, void* dx, void* dres, float* dgamma,
+                                float* dbeta, hipStream_t st) {
+  const BnRows rows = shrink_partials(partials, S, G, C, st);
+  const BnPass p = bn_rows_pass(M, G, C);
   const BnFinBwd fin = {partials, rows.n, rows.stride, S, G, dgamma, dbeta};
-  hipLaunchKernelGGL((bn_dx_kernel<T, true>), grid, dim3(BN_THREADS), 0, st, (const T*)dy, (const T*)x, (const T*)y, (const float*)nullptr,
-                     mean, invstd, gamma, beta, Mg, C, rps2, relu, (T*)dx, (T*)dres, fin);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
-}
-
-template <typename T>
-static int run_bn_fwd(const void* x, const void* res, const float* gamma, const float* beta, float* rmean, float* rvar,
-                      float momentum, float eps, int relu, long long M, int G, int C, void* y, float* save_mean, float* save_invstd,
-                      float* ws, hipStream_t st) {
-  const long long Mg = M / G;                      // rows per statistics group
-  const int S = bn_splits(Mg, C, BN_STAT_BLOCKS, 512), rps = bn_rows_per_split(Mg, S);
-  const int S_eff = (int)((Mg + rps - 1) / rps);
-  hipLaunchKernelGGL((bn_partials_kernel<T, 0>), dim3(C / 64, S_eff, G), dim3(BN_THREADS), 0, st, (const T*)x, (const T*)nullptr,
-                     (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, Mg, C, rps, 0, ws);
-  launch_bn_finalize_apply<T>(x, res, gamma, beta, rmean, rvar, momentum, eps, relu, Mg, G, C, ws, S_eff, y, save_mean, save_invstd, st);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
-}
-
-template <typename T>
-static int run_bn_bwd(const void* dy, const void* x, const void* y, const float* gamma, const float* beta, const float* mean, const float* invstd,
-                      int relu, long long M, int G, int C, void* dx, void* dres, float* dgamma, float* dbeta, float* ws, hipStream_t st) {
-  const long long Mg = M / G;
-  const int S = bn_splits(Mg, C, BN_STAT_BLOCKS, 512), rps = bn_rows_per_split(Mg, S);
-  const int S_eff = (int)((Mg + rps - 1) / rps);
-  hipLaunchKernelGGL((bn_partials_kernel<T, 1>), dim3(C / 64, S_eff, G), dim3(BN_THREADS), 0, st, (const T*)x, (const T*)dy,
-                     (const T*)y, mean, invstd, gamma, beta, Mg, C, rps, relu, ws);
-  const BnRows rows = shrink_partials(ws, S_eff, G, C, st);
-  const int S2 = bn_splits(Mg, C, BN_STAT_BLOCKS, 4096), rps2 = bn_rows_per_split(Mg, S2);
-  const dim3 grid(C / 64, (unsigned)((Mg + rps2 - 1) / rps2), G);
-  const BnFinBwd fin = {ws, rows.n, rows.stride, S_eff, G, dgamma, dbeta};
-  hipLaunchKernelGGL((bn_dx_kernel<T, true>), grid, dim3(BN_THREADS), 0, st, (const T*)dy, (const T*)x, (const T*)y, (const float*)nullptr,
-                     mean, invstd, gamma, beta, Mg, C, rps2, relu, (T*)dx, (T*)dres, fin);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  hipLaunchKernelGGL((bn_dx_kernel<T, true>), p.grid, dim3(BN_THREADS), 0, st, (const T*)in.dy, (const T*)in.x, (const T*)in.y,
+                     (const float*)nullptr, in.mean, in.invstd, in.gamma, in.beta, p.Mg, C, p.rps, in.relu, (T*)dx, (T*)dres, fin);
 }
 
 // ---- staged entry points for synchronised statistics ----
+// the G x C x 2 sums of one rank: statistics pass, shrink, ordered sum of the partial rows
 template <typename T>
-static int run_bn_local_sums(int mode, const void* x, const void* dy, const void* y, const float* gamma, const float* beta,
-                             const float* mean, const float* invstd, int relu, long long M, int G, int C, float* sums, float* ws,
-                             hipStream_t st) {
-  const long long Mg = M / G;
-  const int S = bn_splits(Mg, C, BN_STAT_BLOCKS, 512), rps = bn_rows_per_split(Mg, S);
-  const int S_eff = (int)((Mg + rps - 1) / rps);
-  if (mode == 0)
-    hipLaunchKernelGGL((bn_partials_kernel<T, 0>), dim3(C / 64, S_eff, G), dim3(BN_THREADS), 0, st, (const T*)x, (const T*)nullptr,
-                       (const T*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, Mg, C,
-                       rps, 0, ws);
-  else
-    hipLaunchKernelGGL((bn_partials_kernel<T, 1>), dim3(C / 64, S_eff, G), dim3(BN_THREADS), 0, st, (const T*)x, (const T*)dy,
-                       (const T*)y, mean, invstd, gamma, beta, Mg, C, rps, relu, ws);
-  const BnRows rows = shrink_partials(ws, S_eff, G, C, st);
-  hipLaunchKernelGGL(bn_tile_reduce_kernel, dim3(C / 64), dim3(BN_THREADS), 0, st, (const float*)ws, rows.n, rows.stride, S_eff, C, G, sums);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+static void launch_bn_local_sums(int mode, const BnBwdIn& in, long long M, int G, int C, float* sums, float* ws, hipStream_t st) {
+  const BnPass p = bn_sums_pass(M, G, C);
+  launch_bn_partials<T>(mode, p, in, C, ws, st);
+  const BnRows rows = shrink_partials(ws, p.rows, G, C, st);
+  hipLaunchKernelGGL(bn_tile_reduce_kernel, dim3(C / 64), dim3(BN_THREADS), 0, st, (const float*)ws, rows.n, rows.stride, p.rows, C, G, sums);
 }
 
-template <typename T>
-static int run_bn_sync_apply(const void* x, const void* res, const float* sums, const float* count, const float* gamma, const float* beta,
-                             float* rmean, float* rvar, float momentum, float eps, int relu, long long M, int G, int C, void* y,
-                             float* save_mean, float* save_invstd, hipStream_t st) {
-  const long long Mg = M / G;
-  hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3(C / 64), dim3(64), 0, st, sums, count, C, G, eps, momentum, rmean, rvar, save_mean,
-                     save_invstd);
-  const int S2 = bn_splits(Mg, C, 2048 / G, 4096), rps2 = bn_rows_per_split(Mg, S2);
-  hipLaunchKernelGGL((bn_apply_kernel<T, false>), dim3(C / 64, (unsigned)((Mg + rps2 - 1) / rps2), G), dim3(BN_THREADS), 0, st, (const T*)x,
-                     (const T*)res, gamma, beta, (const float*)save_mean, (const float*)save_invstd, Mg, C, rps2, relu, (T*)y, BnFinFwd{});
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
-}
-
-template <typename T>
-static int run_bn_sync_dx(const void* dy, const void* x, const void* y, const float* local, const float* global, const float* count,
-                          const float* gamma, const float* beta, const float* mean, const float* invstd, int relu, long long M, int G,
-                          int C, void* dx, void* dres, float* dgamma, float* dbeta, float* coef, hipStream_t st) {
-  const long long Mg = M / G;
-  hipLaunchKernelGGL(bn_coef_from_sums_kernel, dim3(C / 64), dim3(64), 0, st, local, global, count, C, G, gamma, mean, invstd, dgamma, dbeta,
-                     coef);
-  const int S2 = bn_splits(Mg, C, 2048 / G, 4096), rps2 = bn_rows_per_split(Mg, S2);
-  hipLaunchKernelGGL((bn_dx_kernel<T, false>), dim3(C / 64, (unsigned)((Mg + rps2 - 1) / rps2), G), dim3(BN_THREADS), 0, st, (const T*)dy,
-                     (const T*)x, (const T*)y, (const float*)coef, mean, invstd, gamma, beta, Mg, C, rps2, relu, (T*)dx, (T*)dres, BnFinBwd{});
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
-}
+// the apply and dx passes of the synchronised form: 2048 workgroups over all groups
+static inline BnPass bn_sync_pass(long long M, int G, int C) { return bn_pass(M, G, C, 2048 / G, 4096); }
 
 }  // namespace td
 
 static bool bn_shape_ok(long long M, int G, int C) { return G >= 1 && G <= 64 && M > 0 && C > 0 && M % G == 0; }
+
+// The checks of every launching entry point, in their order: required pointers, shape and flags (`args_ok`: what the entry point
+// itself requires, evaluated by the caller) are bad arguments; then the limits of the kernels are unsupported shapes.
+static int bn_check(bool args_ok, long long M, int G, int C) {
+  if (!args_ok || !bn_shape_ok(M, G, C)) return TD_ERR_BAD_ARG;
+  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
+  return TD_OK;
+}
+
+// The ReLU mask of a backward entry point: it comes from y, or -- without y -- is recomputed from x (mode 2), which needs beta and,
+// where the entry point has a residual gradient, no dresidual (the residual is not known).  False: bad arguments.
+static bool bn_mask_mode(int* relu, const void* y, const float* beta, const void* dresidual = nullptr) {
+  if (*relu < 0 || *relu > 1) return false;
+  if (*relu && !y && (!beta || dresidual)) return false;
+  if (*relu && !y) *relu = 2;
+  return true;
+}
+
+static bool bn_running_ok(const float* running_mean, const float* running_var) { return (running_mean == nullptr) == (running_var == nullptr); }
 
 extern "C" long long td_bn_workspace_floats(long long M, int groups, int C) {
   if (!bn_shape_ok(M, groups, C) || C % 64 != 0) return 0;
@@ -678,34 +649,36 @@ extern "C" long long td_bn_workspace_floats(long long M, int groups, int C) {
 extern "C" int td_bn_fwd(const void* x, const void* residual, int dtype, const float* gamma, const float* beta,
                          float* running_mean, float* running_var, float momentum, float eps, int relu, long long M, int groups,
                          int C, void* y, float* save_mean, float* save_invstd, float* workspace, td_stream_t stream) {
-  if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !workspace || !bn_shape_ok(M, groups, C)) return TD_ERR_BAD_ARG;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return TD_ERR_BAD_ARG;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_fwd<__hip_bfloat16>(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, M, groups, C, y,
-                                          save_mean, save_invstd, workspace, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_fwd<float>(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, M, groups, C, y, save_mean,
-                                 save_invstd, workspace, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(x && gamma && beta && y && save_mean && save_invstd && workspace && bn_running_ok(running_mean, running_var),
+                          M, groups, C);
+  if (rc != TD_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const td::BnPass p = td::bn_sums_pass(M, groups, C);
+    td::launch_bn_partials<T>(0, p, td::BnBwdIn{nullptr, x}, C, workspace, st);
+    td::launch_bn_finalize_apply<T>(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, M, groups, C, workspace,
+                                    p.rows, y, save_mean, save_invstd, st);
+    return td::launched("td_bn_fwd");
+  });
 }
 
 extern "C" int td_bn_bwd(const void* dy, const void* x, const void* y, int dtype, const float* gamma, const float* beta, const float* save_mean,
                          const float* save_invstd, int relu, long long M, int groups, int C, void* dx, void* dresidual,
                          float* dgamma, float* dbeta, float* workspace, td_stream_t stream) {
-  if (!dy || !x || !gamma || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !workspace || !bn_shape_ok(M, groups, C))
-    return TD_ERR_BAD_ARG;
-  if (relu < 0 || relu > 1) return TD_ERR_BAD_ARG;
-  if (relu && !y && (!beta || dresidual)) return TD_ERR_BAD_ARG;   // the mask comes from y, or is recomputed from x (no residual)
-  if (relu && !y) relu = 2;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_bwd<__hip_bfloat16>(dy, x, y, gamma, beta, save_mean, save_invstd, relu, M, groups, C, dx, dresidual, dgamma, dbeta,
-                                          workspace, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_bwd<float>(dy, x, y, gamma, beta, save_mean, save_invstd, relu, M, groups, C, dx, dresidual, dgamma, dbeta, workspace,
-                                 (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(dy && x && gamma && save_mean && save_invstd && dx && dgamma && dbeta && workspace &&
+                              bn_mask_mode(&relu, y, beta, dresidual),
+                          M, groups, C);
+  if (rc != TD_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const td::BnBwdIn in = {dy, x, y, gamma, beta, save_mean, save_invstd, relu};
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    const td::BnPass p = td::bn_sums_pass(M, groups, C);
+    td::launch_bn_partials<T>(1, p, in, C, workspace, st);
+    td::launch_bn_shrink_dx<T>(in, M, groups, C, workspace, p.rows, dx, dresidual, dgamma, dbeta, st);
+    return td::launched("td_bn_bwd");
+  });
 }
 
 // Forward with the partial sums already formed by the producing kernel (td_conv1x1_fwd's epilogue): the statistics are finished
@@ -715,133 +688,124 @@ extern "C" int td_bn_fwd_from_partials(const void* x, const void* residual, int 
                                        float* running_mean, float* running_var, float momentum, float eps, int relu, long long M,
                                        int groups, int C, float* partials, int stat_rows, void* y, float* save_mean,
                                        float* save_invstd, td_stream_t stream) {
-  if (!x || !gamma || !beta || !y || !save_mean || !save_invstd || !partials || stat_rows < 1 || !bn_shape_ok(M, groups, C))
-    return TD_ERR_BAD_ARG;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return TD_ERR_BAD_ARG;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype != TD_DTYPE_BF16 && dtype != TD_DTYPE_F32) return TD_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const long long Mg = M / groups;
-  if (dtype == TD_DTYPE_BF16)
-    td::launch_bn_finalize_apply<__hip_bfloat16>(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, Mg, groups, C, partials,
-                                                 stat_rows, y, save_mean, save_invstd, st);
-  else
-    td::launch_bn_finalize_apply<float>(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, Mg, groups, C, partials, stat_rows,
-                                        y, save_mean, save_invstd, st);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  const int rc = bn_check(x && gamma && beta && y && save_mean && save_invstd && partials && stat_rows >= 1 &&
+                              bn_running_ok(running_mean, running_var),
+                          M, groups, C);
+  if (rc != TD_OK) return rc;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    td::launch_bn_finalize_apply<T>(x, residual, gamma, beta, running_mean, running_var, momentum, eps, relu, M, groups, C, partials,
+                                    stat_rows, y, save_mean, save_invstd, (hipStream_t)stream);
+    return td::launched("td_bn_fwd_from_partials");
+  });
 }
 
 // ---- the statistics passes on their own (their partial rows are finished by a GEMM prologue or by td_bn_bwd_from_partials) ----
 extern "C" int td_bn_partial_rows(long long M, int groups, int C) {
   if (!bn_shape_ok(M, groups, C) || C % 64 != 0) return 0;
-  return td::bn_stat_rows(M / groups, C);
+  return td::bn_stat_pass(M, groups, C).rows;
 }
 
 extern "C" int td_bn_fwd_partials(const void* x, int dtype, long long M, int groups, int C, float* partials, td_stream_t stream) {
-  if (!x || !partials || !bn_shape_ok(M, groups, C)) return TD_ERR_BAD_ARG;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_partials<__hip_bfloat16>(0, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, M, groups, C, partials, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_partials<float>(0, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, M, groups, C, partials, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(x && partials, M, groups, C);
+  if (rc != TD_OK) return rc;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    td::launch_bn_partials<T>(0, td::bn_stat_pass(M, groups, C), td::BnBwdIn{nullptr, x}, C, partials, (hipStream_t)stream);
+    return td::launched("td_bn_fwd_partials");
+  });
 }
 
 extern "C" int td_bn_bwd_partials(const void* dy, const void* x, const void* y, int dtype, const float* gamma, const float* beta,
                                   const float* save_mean, const float* save_invstd, int relu, long long M, int groups, int C,
                                   float* partials, td_stream_t stream) {
-  if (!dy || !x || !gamma || !save_mean || !save_invstd || !partials || !bn_shape_ok(M, groups, C)) return TD_ERR_BAD_ARG;
-  if (relu < 0 || relu > 1 || (relu && !y && !beta)) return TD_ERR_BAD_ARG;
-  if (relu && !y) relu = 2;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_partials<__hip_bfloat16>(1, x, dy, y, gamma, beta, save_mean, save_invstd, relu, M, groups, C, partials, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_partials<float>(1, x, dy, y, gamma, beta, save_mean, save_invstd, relu, M, groups, C, partials, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(dy && x && gamma && save_mean && save_invstd && partials && bn_mask_mode(&relu, y, beta), M, groups, C);
+  if (rc != TD_OK) return rc;
+  const td::BnBwdIn in = {dy, x, y, gamma, beta, save_mean, save_invstd, relu};
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    td::launch_bn_partials<T>(1, td::bn_stat_pass(M, groups, C), in, C, partials, (hipStream_t)stream);
+    return td::launched("td_bn_bwd_partials");
+  });
 }
 
 extern "C" int td_bn_bwd_from_partials(const void* dy, const void* x, const void* y, int dtype, const float* gamma, const float* beta,
                                        const float* save_mean, const float* save_invstd, int relu, long long M, int groups, int C,
                                        float* partials, int stat_rows, void* dx, void* dresidual, float* dgamma, float* dbeta,
                                        td_stream_t stream) {
-  if (!dy || !x || !gamma || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !partials || stat_rows < 1 || !bn_shape_ok(M, groups, C))
-    return TD_ERR_BAD_ARG;
-  if (relu < 0 || relu > 1) return TD_ERR_BAD_ARG;
-  if (relu && !y && (!beta || dresidual)) return TD_ERR_BAD_ARG;
-  if (relu && !y) relu = 2;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_dx_from_partials<__hip_bfloat16>(dy, x, y, gamma, beta, save_mean, save_invstd, relu, M, groups, C, partials, stat_rows,
-                                                       dx, dresidual, dgamma, dbeta, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_dx_from_partials<float>(dy, x, y, gamma, beta, save_mean, save_invstd, relu, M, groups, C, partials, stat_rows, dx,
-                                              dresidual, dgamma, dbeta, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(dy && x && gamma && save_mean && save_invstd && dx && dgamma && dbeta && partials && stat_rows >= 1 &&
+                              bn_mask_mode(&relu, y, beta, dresidual),
+                          M, groups, C);
+  if (rc != TD_OK) return rc;
+  const td::BnBwdIn in = {dy, x, y, gamma, beta, save_mean, save_invstd, relu};
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    td::launch_bn_shrink_dx<T>(in, M, groups, C, partials, stat_rows, dx, dresidual, dgamma, dbeta, (hipStream_t)stream);
+    return td::launched("td_bn_bwd_from_partials");
+  });
 }
 
 // ---- synchronised (cross-rank) statistics: local sums -> [caller: all-reduce] -> apply / dx --------------------
 
 extern "C" int td_bn_sync_fwd_sums(const void* x, int dtype, long long M, int groups, int C, float* sums, float* workspace,
                                    td_stream_t stream) {
-  if (!x || !sums || !workspace || !bn_shape_ok(M, groups, C)) return TD_ERR_BAD_ARG;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_local_sums<__hip_bfloat16>(0, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, M, groups, C, sums, workspace,
-                                                 (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_local_sums<float>(0, x, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, M, groups, C, sums, workspace,
-                                        (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(x && sums && workspace, M, groups, C);
+  if (rc != TD_OK) return rc;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    td::launch_bn_local_sums<T>(0, td::BnBwdIn{nullptr, x}, M, groups, C, sums, workspace, (hipStream_t)stream);
+    return td::launched("td_bn_sync_fwd_sums");
+  });
 }
 
 extern "C" int td_bn_sync_fwd_apply(const void* x, const void* residual, int dtype, const float* sums, const float* count,
                                     const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
                                     float eps, int relu, long long M, int groups, int C, void* y, float* save_mean, float* save_invstd,
                                     td_stream_t stream) {
-  if (!x || !sums || !count || !gamma || !beta || !y || !save_mean || !save_invstd || !bn_shape_ok(M, groups, C)) return TD_ERR_BAD_ARG;
-  if ((running_mean == nullptr) != (running_var == nullptr)) return TD_ERR_BAD_ARG;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_sync_apply<__hip_bfloat16>(x, residual, sums, count, gamma, beta, running_mean, running_var, momentum, eps, relu, M,
-                                                 groups, C, y, save_mean, save_invstd, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_sync_apply<float>(x, residual, sums, count, gamma, beta, running_mean, running_var, momentum, eps, relu, M, groups, C,
-                                        y, save_mean, save_invstd, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(x && sums && count && gamma && beta && y && save_mean && save_invstd && bn_running_ok(running_mean, running_var),
+                          M, groups, C);
+  if (rc != TD_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(td::bn_stats_from_sums_kernel, dim3(C / 64), dim3(64), 0, st, sums, count, C, groups, eps, momentum, running_mean,
+                       running_var, save_mean, save_invstd);
+    const td::BnPass p = td::bn_sync_pass(M, groups, C);
+    hipLaunchKernelGGL((td::bn_apply_kernel<T, false>), p.grid, dim3(td::BN_THREADS), 0, st, (const T*)x, (const T*)residual, gamma, beta,
+                       (const float*)save_mean, (const float*)save_invstd, p.Mg, C, p.rps, relu, (T*)y, td::BnFinFwd{});
+    return td::launched("td_bn_sync_fwd_apply");
+  });
 }
 
 extern "C" int td_bn_sync_bwd_sums(const void* dy, const void* x, const void* y, int dtype, const float* gamma, const float* beta,
                                    const float* save_mean, const float* save_invstd, int relu, long long M, int groups, int C,
                                    float* sums, float* workspace, td_stream_t stream) {
-  if (!dy || !x || !gamma || !save_mean || !save_invstd || !sums || !workspace || !bn_shape_ok(M, groups, C)) return TD_ERR_BAD_ARG;
-  if (relu < 0 || relu > 1 || (relu && !y && !beta)) return TD_ERR_BAD_ARG;
-  if (relu && !y) relu = 2;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_local_sums<__hip_bfloat16>(1, x, dy, y, gamma, beta, save_mean, save_invstd, relu, M, groups, C, sums, workspace,
-                                                 (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_local_sums<float>(1, x, dy, y, gamma, beta, save_mean, save_invstd, relu, M, groups, C, sums, workspace,
-                                        (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(dy && x && gamma && save_mean && save_invstd && sums && workspace && bn_mask_mode(&relu, y, beta), M, groups, C);
+  if (rc != TD_OK) return rc;
+  const td::BnBwdIn in = {dy, x, y, gamma, beta, save_mean, save_invstd, relu};
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    td::launch_bn_local_sums<T>(1, in, M, groups, C, sums, workspace, (hipStream_t)stream);
+    return td::launched("td_bn_sync_bwd_sums");
+  });
 }
 
 extern "C" int td_bn_sync_bwd_dx(const void* dy, const void* x, const void* y, int dtype, const float* local_sums, const float* global_sums,
                                  const float* count, const float* gamma, const float* beta, const float* save_mean,
                                  const float* save_invstd, int relu, long long M, int groups, int C, void* dx, void* dresidual,
                                  float* dgamma, float* dbeta, float* coef, td_stream_t stream) {
-  if (!dy || !x || !local_sums || !global_sums || !count || !gamma || !save_mean || !save_invstd || !dx || !dgamma || !dbeta || !coef ||
-      !bn_shape_ok(M, groups, C))
-    return TD_ERR_BAD_ARG;
-  if (relu < 0 || relu > 1 || (relu && !y && (!beta || dresidual))) return TD_ERR_BAD_ARG;
-  if (relu && !y) relu = 2;
-  if (C % 64 != 0 || M * (long long)C >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_bn_sync_dx<__hip_bfloat16>(dy, x, y, local_sums, global_sums, count, gamma, beta, save_mean, save_invstd, relu, M, groups,
-                                              C, dx, dresidual, dgamma, dbeta, coef, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_bn_sync_dx<float>(dy, x, y, local_sums, global_sums, count, gamma, beta, save_mean, save_invstd, relu, M, groups, C, dx,
-                                     dresidual, dgamma, dbeta, coef, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  const int rc = bn_check(dy && x && local_sums && global_sums && count && gamma && save_mean && save_invstd && dx && dgamma && dbeta &&
+                              coef && bn_mask_mode(&relu, y, beta, dresidual),
+                          M, groups, C);
+  if (rc != TD_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL(td::bn_coef_from_sums_kernel, dim3(C / 64), dim3(64), 0, st, local_sums, global_sums, count, C, groups, gamma,
+                       save_mean, save_invstd, dgamma, dbeta, coef);
+    const td::BnPass p = td::bn_sync_pass(M, groups, C);
+    hipLaunchKernelGGL((td::bn_dx_kernel<T, false>), p.grid, dim3(td::BN_THREADS), 0, st, (const T*)dy, (const T*)x, (const T*)y,
+                       (const float*)coef, save_mean, save_invstd, gamma, beta, p.Mg, C, p.rps, relu, (T*)dx, (T*)dresidual, td::BnFinBwd{});
+    return td::launched("td_bn_sync_bwd_dx");
+  });
 }

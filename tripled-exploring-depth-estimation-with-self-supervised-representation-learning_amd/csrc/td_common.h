@@ -1,5 +1,6 @@
 // Shared device helpers for libtripled_hip (gfx950 / CDNA4, wave64).
 #pragma once
+#include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -17,6 +18,20 @@
 namespace td {
 
 int record_launch_error(hipError_t e, const char* what);
+
+// status of the launches an entry point just enqueued, recorded under its name (`what`: the extern "C" name the caller called)
+static inline int launched(const char* what) { return record_launch_error(hipGetLastError(), what); }
+
+// dtype code -> element type: f(TypeTag<T>{}) with T = __hip_bfloat16 or float, for entry points whose two branches are one call;
+// any other code is unsupported.  In the callable: using T = typename decltype(tag)::type.
+template <typename T>
+struct TypeTag { using type = T; };
+template <typename F>
+static inline int dispatch_dtype(int dtype, F&& f) {
+  if (dtype == TD_DTYPE_BF16) return f(TypeTag<__hip_bfloat16>{});
+  if (dtype == TD_DTYPE_F32) return f(TypeTag<float>{});
+  return TD_ERR_UNSUPPORTED;
+}
 
 // the partial rows a consumer prologue sums: rows 0, stride, 2 stride, ... (n of them)
 struct BnRows { int n, stride; };

@@ -580,14 +580,15 @@ __global__ __launch_bounds__(TD_THREADS) void conv1x1_wgrad_reduce_group_kernel(
   }
 }
 
-// dW = ordered sum of P fp32 slabs of NK elements, rounded once to the weight's dtype (shared with td_conv3x3_wgrad.hip)
-int cv_wgrad_reduce(const float* part, int P, long long NK, int dw_dtype, void* dw, hipStream_t st) {
+// dW = ordered sum of P fp32 slabs of NK elements, rounded once to the weight's dtype (shared with td_conv3x3_wgrad.hip);
+// returns the status of everything the entry point `what` has launched so far
+int cv_wgrad_reduce(const float* part, int P, long long NK, int dw_dtype, void* dw, hipStream_t st, const char* what) {
   const unsigned blocks = (unsigned)((NK / 4 + 15) / 16);
-  if (dw_dtype == TD_DTYPE_BF16)
-    hipLaunchKernelGGL((conv1x1_wgrad_reduce_kernel<__hip_bfloat16>), dim3(blocks), dim3(TD_THREADS), 0, st, part, P, NK, (__hip_bfloat16*)dw);
-  else
-    hipLaunchKernelGGL((conv1x1_wgrad_reduce_kernel<float>), dim3(blocks), dim3(TD_THREADS), 0, st, part, P, NK, (float*)dw);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  return dispatch_dtype(dw_dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    hipLaunchKernelGGL((conv1x1_wgrad_reduce_kernel<T>), dim3(blocks), dim3(TD_THREADS), 0, st, part, P, NK, (T*)dw);
+    return launched(what);
+  });
 }
 
 static inline int wg_splits(long long M, int K, int N) {
@@ -601,39 +602,52 @@ static inline int wg_splits(long long M, int K, int N) {
 
 template <int BM, int BN, bool BT, int PRO, int EPI, bool DEEP>
 static int cv_launch(const void* x, const void* w, void* y, float* ws, long long Mg, int G, int K, int N, ConvRows geom, hipStream_t st,
-                     const CvFuse& fz) {
+                     const CvFuse& fz, const char* what) {
   const int tpg = (int)((Mg + BM - 1) / BM);
   const long long nblk = (long long)G * tpg * (N / BN);
   if (nblk > 0x7fffffffll) return TD_ERR_UNSUPPORTED;
   hipLaunchKernelGGL((conv1x1_mfma_kernel<BM, BN, BT, PRO, EPI, DEEP>), dim3((unsigned)nblk), dim3(CV_THREADS), 0, st, (const __hip_bfloat16*)x,
                      (const __hip_bfloat16*)w, (__hip_bfloat16*)y, ws, Mg, K, N, tpg, (int)nblk, geom, fz);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  return launched(what);
 }
 
 // tile choice as the plain forward; one instantiation set per fused form
 template <bool BT, int PRO, int EPI>
 static int cv_dispatch(const void* x, const void* w, void* y, float* ws, long long M, int G, int K, int N, ConvRows geom, hipStream_t st,
-                       const CvFuse& fz) {
+                       const CvFuse& fz, const char* what) {
   const long long Mg = M / G;
   ConvTile t = cv_pick_tile(Mg, G, N);
   const bool deep = K >= 3 * CV_BK;
   if constexpr (PRO == 2) {      // its prologue coefficients + the transposed weight stage leave no room for two 128 x 128 blocks per CU
     if (t.bm == 128 && t.bn == 128) t.bn = 64;
   } else
-    if (t.bm == 128 && t.bn == 128) return cv_launch<128, 128, BT, PRO, EPI, false>(x, w, y, ws, Mg, G, K, N, geom, st, fz);
+    if (t.bm == 128 && t.bn == 128) return cv_launch<128, 128, BT, PRO, EPI, false>(x, w, y, ws, Mg, G, K, N, geom, st, fz, what);
   if (t.bm == 128 && t.bn == 64) {
     if constexpr (PRO == 0)
-      if (deep) return cv_launch<128, 64, BT, PRO, EPI, true>(x, w, y, ws, Mg, G, K, N, geom, st, fz);
-    return cv_launch<128, 64, BT, PRO, EPI, false>(x, w, y, ws, Mg, G, K, N, geom, st, fz);
+      if (deep) return cv_launch<128, 64, BT, PRO, EPI, true>(x, w, y, ws, Mg, G, K, N, geom, st, fz, what);
+    return cv_launch<128, 64, BT, PRO, EPI, false>(x, w, y, ws, Mg, G, K, N, geom, st, fz, what);
   }
-  if (deep) return cv_launch<64, 64, BT, PRO, EPI, true>(x, w, y, ws, Mg, G, K, N, geom, st, fz);
-  return cv_launch<64, 64, BT, PRO, EPI, false>(x, w, y, ws, Mg, G, K, N, geom, st, fz);
+  if (deep) return cv_launch<64, 64, BT, PRO, EPI, true>(x, w, y, ws, Mg, G, K, N, geom, st, fz, what);
+  return cv_launch<64, 64, BT, PRO, EPI, false>(x, w, y, ws, Mg, G, K, N, geom, st, fz, what);
 }
 
 }  // namespace td
 
 static bool cv_shape_ok(long long M, int G, int K, int N) {
   return M > 0 && G >= 1 && G <= 64 && M % G == 0 && K > 0 && N > 0 && K % 64 == 0 && N % 64 == 0;
+}
+
+// The M output rows of a 1x1 convolution of stride `stride` over [*, Hi, Wi] inputs (stride 1: the identity, Hi and Wi unused);
+// false when the arguments describe no such convolution.
+static bool cv_strided_rows(long long M, int Hi, int Wi, int stride, td::ConvRows* geom) {
+  *geom = {0, 0, 0, 0, 1};
+  if (stride < 1) return false;
+  if (stride == 1) return true;
+  if (Hi <= 0 || Wi <= 0) return false;
+  const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
+  if (M % ((long long)Ho * Wo) != 0) return false;
+  *geom = {Wo, Ho * Wo, Wi, Hi * Wi, stride};
+  return true;
 }
 
 extern "C" int td_conv1x1_stat_rows(long long M, int groups, int N) {
@@ -644,16 +658,10 @@ extern "C" int td_conv1x1_stat_rows(long long M, int groups, int N) {
 
 extern "C" int td_conv1x1_fwd(const void* x, const void* w, long long M, int groups, int K, int N, int Hi, int Wi, int stride, void* y,
                               float* stat_partials, td_stream_t stream) {
-  if (!x || !w || !y || !cv_shape_ok(M, groups, K, N) || stride < 1) return TD_ERR_BAD_ARG;
-  td::ConvRows geom = {0, 0, 0, 0, 1};
-  if (stride > 1) {
-    if (Hi <= 0 || Wi <= 0) return TD_ERR_BAD_ARG;
-    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-    if (M % ((long long)Ho * Wo) != 0) return TD_ERR_BAD_ARG;
-    geom = {Wo, Ho * Wo, Wi, Hi * Wi, stride};
-  }
+  td::ConvRows geom;
+  if (!x || !w || !y || !cv_shape_ok(M, groups, K, N) || !cv_strided_rows(M, Hi, Wi, stride, &geom)) return TD_ERR_BAD_ARG;
   if (M * (long long)(K > N ? K : N) >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  return td::cv_dispatch<false, 0, 0>(x, w, y, stat_partials, M, groups, K, N, geom, (hipStream_t)stream, td::CvFuse{});
+  return td::cv_dispatch<false, 0, 0>(x, w, y, stat_partials, M, groups, K, N, geom, (hipStream_t)stream, td::CvFuse{}, "td_conv1x1_fwd");
 }
 
 // partial rows (any producer) reduced in place to at most CV_PRO_MAX_S rows for a GEMM prologue; returns (rows, stride)
@@ -675,7 +683,7 @@ extern "C" int td_conv1x1_fwd_bnrelu(const void* z, const void* w, long long M, 
   fz.part = in_partials; fz.part_S = rows.n; fz.part_stride = rows.stride; fz.part_rows = in_rows;
   fz.gamma = gamma; fz.beta = beta; fz.mean = save_mean; fz.invstd = save_invstd; fz.rmean = running_mean; fz.rvar = running_var;
   fz.momentum = momentum; fz.eps = eps; fz.a_side = (__hip_bfloat16*)a_side; fz.G = groups;
-  return td::cv_dispatch<false, 1, 0>(z, w, y, stat_partials, M, groups, K, N, td::ConvRows{0, 0, 0, 0, 1}, st, fz);
+  return td::cv_dispatch<false, 1, 0>(z, w, y, stat_partials, M, groups, K, N, td::ConvRows{0, 0, 0, 0, 1}, st, fz, "td_conv1x1_fwd_bnrelu");
 }
 
 // y = conv1x1(x, w) and run_out = run_in + y in one launch (the CRP block's pointwise convolution + running sum)
@@ -686,7 +694,7 @@ extern "C" int td_conv1x1_fwd_sum(const void* x, const void* w, long long M, int
   td::CvFuse fz = {};
   fz.ep.res = (const __hip_bfloat16*)run_in;
   fz.ep.y2 = (__hip_bfloat16*)run_out;
-  return td::cv_dispatch<false, 0, 3>(x, w, y, nullptr, M, 1, K, N, td::ConvRows{0, 0, 0, 0, 1}, (hipStream_t)stream, fz);
+  return td::cv_dispatch<false, 0, 3>(x, w, y, nullptr, M, 1, K, N, td::ConvRows{0, 0, 0, 0, 1}, (hipStream_t)stream, fz, "td_conv1x1_fwd_sum");
 }
 
 // Data gradient dX[M, Cin] = dY[M, Cout] . W[Cout, Cin] (stride 1).
@@ -697,8 +705,8 @@ extern "C" int td_conv1x1_dgrad(const void* dy, const void* w, long long M, int 
   td::CvFuse fz = {};
   fz.ep.res = (const __hip_bfloat16*)residual;
   const td::ConvRows geom = {0, 0, 0, 0, 1};
-  if (residual) return td::cv_dispatch<true, 0, 1>(dy, w, dx, nullptr, M, groups, Cout, Cin, geom, (hipStream_t)stream, fz);
-  return td::cv_dispatch<true, 0, 0>(dy, w, dx, nullptr, M, groups, Cout, Cin, geom, (hipStream_t)stream, fz);
+  if (residual) return td::cv_dispatch<true, 0, 1>(dy, w, dx, nullptr, M, groups, Cout, Cin, geom, (hipStream_t)stream, fz, "td_conv1x1_dgrad");
+  return td::cv_dispatch<true, 0, 0>(dy, w, dx, nullptr, M, groups, Cout, Cin, geom, (hipStream_t)stream, fz, "td_conv1x1_dgrad");
 }
 
 extern "C" int td_conv1x1_dgrad_bnsums(const void* dy, const void* w, long long M, int groups, int Cout, int Cin, const void* z,
@@ -709,7 +717,7 @@ extern "C" int td_conv1x1_dgrad_bnsums(const void* dy, const void* w, long long 
   if (M * (long long)(Cout > Cin ? Cout : Cin) >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
   td::CvFuse fz = {};
   fz.ep.z = (const __hip_bfloat16*)z; fz.ep.gamma = gamma; fz.ep.beta = beta; fz.ep.mean = save_mean; fz.ep.invstd = save_invstd;
-  return td::cv_dispatch<true, 0, 2>(dy, w, dx, out_partials, M, groups, Cout, Cin, td::ConvRows{0, 0, 0, 0, 1}, (hipStream_t)stream, fz);
+  return td::cv_dispatch<true, 0, 2>(dy, w, dx, out_partials, M, groups, Cout, Cin, td::ConvRows{0, 0, 0, 0, 1}, (hipStream_t)stream, fz, "td_conv1x1_dgrad_bnsums");
 }
 
 extern "C" int td_conv1x1_dgrad_bnbwd(const void* g, const void* z, const void* w, long long M, int groups, int Cout, int Cin,
@@ -728,8 +736,8 @@ extern "C" int td_conv1x1_dgrad_bnbwd(const void* g, const void* z, const void* 
   fz.dgamma = dgamma; fz.dbeta = dbeta; fz.a_side = (__hip_bfloat16*)dz_side; fz.G = groups;
   fz.ep.res = (const __hip_bfloat16*)residual;
   const td::ConvRows geom = {0, 0, 0, 0, 1};
-  if (residual) return td::cv_dispatch<true, 2, 1>(g, w, dx, nullptr, M, groups, Cout, Cin, geom, st, fz);
-  return td::cv_dispatch<true, 2, 0>(g, w, dx, nullptr, M, groups, Cout, Cin, geom, st, fz);
+  if (residual) return td::cv_dispatch<true, 2, 1>(g, w, dx, nullptr, M, groups, Cout, Cin, geom, st, fz, "td_conv1x1_dgrad_bnbwd");
+  return td::cv_dispatch<true, 2, 0>(g, w, dx, nullptr, M, groups, Cout, Cin, geom, st, fz, "td_conv1x1_dgrad_bnbwd");
 }
 
 extern "C" long long td_conv1x1_wgrad_workspace_floats(long long M, int K, int N) {
@@ -737,55 +745,52 @@ extern "C" long long td_conv1x1_wgrad_workspace_floats(long long M, int K, int N
   return (long long)td::wg_splits(M, K, N) * N * K;
 }
 
-extern "C" int td_conv1x1_wgrad(const void* dy, const void* x, long long M, int K, int N, int Hi, int Wi, int stride, int dw_dtype,
-                                void* dw, float* workspace, td_stream_t stream) {
-  if (!dy || !x || !dw || !workspace || M <= 0 || K <= 0 || N <= 0 || K % 64 != 0 || N % 64 != 0 || stride < 1) return TD_ERR_BAD_ARG;
+// One weight-gradient problem: its checks (in the order of td_conv1x1_wgrad) and how it is cut.  A pure function of the shape, and
+// the ONLY statement of it: the single and the grouped entry point both launch what it returns.
+struct WgPlan {
+  td::ConvRows geom;
+  int rps, P_eff, tiles_n, tiles_k;      // rows per slab (a multiple of WG_T), slabs written, 64 x 64 tiles of dW
+};
+static int wg_plan(long long M, int K, int N, int Hi, int Wi, int stride, int dw_dtype, WgPlan* p) {
+  if (M <= 0 || K <= 0 || N <= 0 || K % 64 != 0 || N % 64 != 0 || stride < 1) return TD_ERR_BAD_ARG;
   if (dw_dtype != TD_DTYPE_BF16 && dw_dtype != TD_DTYPE_F32) return TD_ERR_UNSUPPORTED;
-  td::ConvRows geom = {0, 0, 0, 0, 1};
-  if (stride > 1) {
-    if (Hi <= 0 || Wi <= 0) return TD_ERR_BAD_ARG;
-    const int Ho = (Hi - 1) / stride + 1, Wo = (Wi - 1) / stride + 1;
-    if (M % ((long long)Ho * Wo) != 0) return TD_ERR_BAD_ARG;
-    geom = {Wo, Ho * Wo, Wi, Hi * Wi, stride};
-  }
+  if (!cv_strided_rows(M, Hi, Wi, stride, &p->geom)) return TD_ERR_BAD_ARG;
   if (M * (long long)(K > N ? K : N) >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
   const int P = td::wg_splits(M, K, N);
   long long rps = (M + P - 1) / P;
   rps = (rps + td::WG_T - 1) / td::WG_T * td::WG_T;
-  const int P_eff = (int)((M + rps - 1) / rps);          // (<= P: trailing empty ranges are not launched; the reduce reads P_eff slabs)
-  const int tn = N / td::WG_T, tk = K / td::WG_T;
-  hipLaunchKernelGGL(td::conv1x1_wgrad_kernel, dim3((unsigned)(tn * tk * P_eff)), dim3(td::CV_THREADS), 0, st, (const __hip_bfloat16*)dy,
-                     (const __hip_bfloat16*)x, workspace, M, K, N, (int)rps, tn, tk, geom);
-  const long long NK = (long long)N * K;
-  const unsigned blocks = (unsigned)((NK / 4 + 15) / 16);
-  if (dw_dtype == TD_DTYPE_BF16)
-    hipLaunchKernelGGL((td::conv1x1_wgrad_reduce_kernel<__hip_bfloat16>), dim3(blocks), dim3(TD_THREADS), 0, st, (const float*)workspace, P_eff,
-                       NK, (__hip_bfloat16*)dw);
-  else
-    hipLaunchKernelGGL((td::conv1x1_wgrad_reduce_kernel<float>), dim3(blocks), dim3(TD_THREADS), 0, st, (const float*)workspace, P_eff, NK,
-                       (float*)dw);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  p->rps = (int)rps;
+  p->P_eff = (int)((M + rps - 1) / rps);          // (<= P: trailing empty ranges are not launched; the reduce reads P_eff slabs)
+  p->tiles_n = N / td::WG_T;
+  p->tiles_k = K / td::WG_T;
+  return TD_OK;
+}
+
+extern "C" int td_conv1x1_wgrad(const void* dy, const void* x, long long M, int K, int N, int Hi, int Wi, int stride, int dw_dtype,
+                                void* dw, float* workspace, td_stream_t stream) {
+  if (!dy || !x || !dw || !workspace) return TD_ERR_BAD_ARG;
+  WgPlan p;
+  const int rc = wg_plan(M, K, N, Hi, Wi, stride, dw_dtype, &p);
+  if (rc != TD_OK) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(td::conv1x1_wgrad_kernel, dim3((unsigned)(p.tiles_n * p.tiles_k * p.P_eff)), dim3(td::CV_THREADS), 0, st,
+                     (const __hip_bfloat16*)dy, (const __hip_bfloat16*)x, workspace, M, K, N, p.rps, p.tiles_n, p.tiles_k, p.geom);
+  return td::cv_wgrad_reduce(workspace, p.P_eff, (long long)N * K, dw_dtype, dw, st, "td_conv1x1_wgrad");
 }
 
 // Grouped weight gradients: problem i is exactly td_conv1x1_wgrad(dy[i], x[i], M[i], K[i], N[i], Hi[i], Wi[i], stride[i], dw_dtype[i],
-// dw[i], workspace[i]) -- same tiling, same row ranges, same summation order, bit-equal results -- but <= 40 problems share a launch
-// (and <= 96 slab sums).  All array arguments are HOST arrays of length n.
+// dw[i], workspace[i]) -- the same wg_plan, hence the same tiling, row ranges and summation order and bit-equal results -- but <= 40
+// problems share a launch (and <= 96 slab sums).  All array arguments are HOST arrays of length n.
 extern "C" int td_conv1x1_wgrad_group(int n, const void* const* dy, const void* const* x, const long long* M, const int* K, const int* N,
                                       const int* Hi, const int* Wi, const int* stride, const int* dw_dtype, void* const* dw,
                                       float* const* workspace, td_stream_t stream) {
   if (n < 0 || (n > 0 && (!dy || !x || !M || !K || !N || !Hi || !Wi || !stride || !dw_dtype || !dw || !workspace))) return TD_ERR_BAD_ARG;
   hipStream_t st = (hipStream_t)stream;
-  for (int i = 0; i < n; ++i) {
-    if (!dy[i] || !x[i] || !dw[i] || !workspace[i] || M[i] <= 0 || K[i] <= 0 || N[i] <= 0 || K[i] % 64 != 0 || N[i] % 64 != 0 || stride[i] < 1)
-      return TD_ERR_BAD_ARG;
-    if (dw_dtype[i] != TD_DTYPE_BF16 && dw_dtype[i] != TD_DTYPE_F32) return TD_ERR_UNSUPPORTED;
-    if (M[i] * (long long)(K[i] > N[i] ? K[i] : N[i]) >= (1ll << 40)) return TD_ERR_UNSUPPORTED;
-    if (stride[i] > 1) {
-      if (Hi[i] <= 0 || Wi[i] <= 0) return TD_ERR_BAD_ARG;
-      const int Ho = (Hi[i] - 1) / stride[i] + 1, Wo = (Wi[i] - 1) / stride[i] + 1;
-      if (M[i] % ((long long)Ho * Wo) != 0) return TD_ERR_BAD_ARG;
-    }
+  WgPlan p;
+  for (int i = 0; i < n; ++i) {      // the first failing problem decides
+    if (!dy[i] || !x[i] || !dw[i] || !workspace[i]) return TD_ERR_BAD_ARG;
+    const int rc = wg_plan(M[i], K[i], N[i], Hi[i], Wi[i], stride[i], dw_dtype[i], &p);
+    if (rc != TD_OK) return rc;
   }
   int P_eff[4096];
   if (n > 4096) return TD_ERR_UNSUPPORTED;
@@ -795,18 +800,11 @@ extern "C" int td_conv1x1_wgrad_group(int n, const void* const* dy, const void* 
     long long blocks = 0;
     for (int j = 0; j < a.n; ++j) {
       const int i = base + j;
-      td::ConvRows geom = {0, 0, 0, 0, 1};
-      if (stride[i] > 1) {
-        const int Ho = (Hi[i] - 1) / stride[i] + 1, Wo = (Wi[i] - 1) / stride[i] + 1;
-        geom = {Wo, Ho * Wo, Wi[i], Hi[i] * Wi[i], stride[i]};
-      }
-      const int P = td::wg_splits(M[i], K[i], N[i]);
-      long long rps = (M[i] + P - 1) / P;
-      rps = (rps + td::WG_T - 1) / td::WG_T * td::WG_T;
-      P_eff[i] = (int)((M[i] + rps - 1) / rps);
+      wg_plan(M[i], K[i], N[i], Hi[i], Wi[i], stride[i], dw_dtype[i], &p);      // checked above
+      P_eff[i] = p.P_eff;
       td::WgProblem& q = a.p[j];
       q.dy = (const __hip_bfloat16*)dy[i]; q.x = (const __hip_bfloat16*)x[i]; q.part = workspace[i]; q.M = M[i]; q.K = K[i]; q.N = N[i];
-      q.rows_per_split = (int)rps; q.tiles_n = N[i] / td::WG_T; q.tiles_k = K[i] / td::WG_T; q.geom = geom;
+      q.rows_per_split = p.rps; q.tiles_n = p.tiles_n; q.tiles_k = p.tiles_k; q.geom = p.geom;
       a.first_block[j] = (int)blocks;
       blocks += (long long)q.tiles_n * q.tiles_k * P_eff[i];
       if (blocks > 0x7fffffffll) return TD_ERR_UNSUPPORTED;
@@ -828,5 +826,5 @@ extern "C" int td_conv1x1_wgrad_group(int n, const void* const* dy, const void* 
     for (int j = a.n; j <= td::RD_GROUP_MAX; ++j) a.first_block[j] = (int)blocks;
     hipLaunchKernelGGL(td::conv1x1_wgrad_reduce_group_kernel, dim3((unsigned)blocks), dim3(TD_THREADS), 0, st, a);
   }
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  return td::launched("td_conv1x1_wgrad_group");
 }

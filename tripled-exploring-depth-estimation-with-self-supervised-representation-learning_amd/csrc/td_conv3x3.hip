@@ -124,7 +124,7 @@ static int c3_launch(const void* x, const void* w, void* y, float* ws, long long
   if (nblk > 0x7fffffffll) return TD_ERR_UNSUPPORTED;
   hipLaunchKernelGGL((conv3x3_mfma_kernel<BM, BN>), dim3((unsigned)nblk), dim3(CV_THREADS), 0, st, (const __hip_bfloat16*)x,
                      (const __hip_bfloat16*)w, (__hip_bfloat16*)y, ws, Mg, N, tpg, (int)nblk, g);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  return launched("td_conv3x3_fwd");
 }
 
 }  // namespace td

@@ -197,7 +197,7 @@ __global__ __launch_bounds__(W3_THREADS, 2) void conv3x3_wgrad_kernel(
 }
 
 // defined in td_conv1x1.hip: dW = ordered sum of P fp32 slabs, rounded once
-int cv_wgrad_reduce(const float* part, int P, long long NK, int dw_dtype, void* dw, hipStream_t st);
+int cv_wgrad_reduce(const float* part, int P, long long NK, int dw_dtype, void* dw, hipStream_t st, const char* what);
 
 static inline int w3_splits(long long M, int C, int N) {
   const long long tiles = (long long)(N / W3_T) * (C / W3_T);
@@ -241,6 +241,7 @@ extern "C" int td_conv3x3_wgrad(const void* dy, const void* x, int B, int Ho, in
   else
     hipLaunchKernelGGL((td::conv3x3_wgrad_kernel<0>), grid, dim3(td::W3_THREADS), 0, st, (const __hip_bfloat16*)dy, (const __hip_bfloat16*)x,
                        workspace, M, Ho, Wo, C, N, (int)rps, tn, tc);
-  if (hipGetLastError() != hipSuccess) return TD_ERR_LAUNCH;
-  return td::cv_wgrad_reduce(workspace, P_eff, (long long)N * 9 * C, dw_dtype, dw, st);
+  const int rc = td::launched("td_conv3x3_wgrad");
+  if (rc != TD_OK) return rc;
+  return td::cv_wgrad_reduce(workspace, P_eff, (long long)N * 9 * C, dw_dtype, dw, st, "td_conv3x3_wgrad");
 }

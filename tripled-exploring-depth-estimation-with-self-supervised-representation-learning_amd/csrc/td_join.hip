@@ -116,7 +116,7 @@ __global__ __launch_bounds__(TD_THREADS) void join_up2_kernel(T* __restrict__ a,
 }
 
 template <typename T>
-static int run_join_up2(bool fwd, void* a, void* b, void* t, int N, int H, int W, int C0, int C1, int C2, void* out, hipStream_t st) {
+static int run_join_up2(const char* what, bool fwd, void* a, void* b, void* t, int N, int H, int W, int C0, int C1, int C2, void* out, hipStream_t st) {
   const long long npix = (long long)N * H * W;
   const int n0 = C0 / 8, n1 = C1 / 8;
   const long long total = fwd ? npix * (n0 + n1 + 1) : npix * (n0 + 1) + npix / 4 * n1;
@@ -125,18 +125,18 @@ static int run_join_up2(bool fwd, void* a, void* b, void* t, int N, int H, int W
     hipLaunchKernelGGL((join_up2_kernel<T, true>), dim3(blocks), dim3(TD_THREADS), 0, st, (T*)a, (T*)b, (T*)t, N, H, W, C0, C1, C2, (T*)out);
   else
     hipLaunchKernelGGL((join_up2_kernel<T, false>), dim3(blocks), dim3(TD_THREADS), 0, st, (T*)a, (T*)b, (T*)t, N, H, W, C0, C1, C2, (T*)out);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  return launched(what);
 }
 
 template <typename T>
-static int run_join(bool fwd, void* a, void* b, void* t, long long npix, int C0, int C1, int C2, void* out, hipStream_t st) {
+static int run_join(const char* what, bool fwd, void* a, void* b, void* t, long long npix, int C0, int C1, int C2, void* out, hipStream_t st) {
   const long long total = npix * (C0 / 8 + C1 / 8 + 1);
   const unsigned blocks = (unsigned)((total + TD_THREADS - 1) / TD_THREADS);
   if (fwd)
     hipLaunchKernelGGL((join_kernel<T, true>), dim3(blocks), dim3(TD_THREADS), 0, st, (T*)a, (T*)b, (T*)t, npix, C0, C1, C2, (T*)out);
   else
     hipLaunchKernelGGL((join_kernel<T, false>), dim3(blocks), dim3(TD_THREADS), 0, st, (T*)a, (T*)b, (T*)t, npix, C0, C1, C2, (T*)out);
-  return hipGetLastError() == hipSuccess ? TD_OK : TD_ERR_LAUNCH;
+  return launched(what);
 }
 
 }  // namespace td
@@ -151,20 +151,20 @@ extern "C" int td_join_fwd(const void* a, const void* b, const void* tail, int d
                            void* out, td_stream_t stream) {
   const int rc = join_check(a, b, tail, out, npix, C0, C1, C2);
   if (rc != TD_OK) return rc;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_join<__hip_bfloat16>(true, (void*)a, (void*)b, (void*)tail, npix, C0, C1, C2, out, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32) return td::run_join<float>(true, (void*)a, (void*)b, (void*)tail, npix, C0, C1, C2, out, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return td::run_join<T>("td_join_fwd", true, (void*)a, (void*)b, (void*)tail, npix, C0, C1, C2, out, (hipStream_t)stream);
+  });
 }
 
 extern "C" int td_join_bwd(const void* grad_out, int dtype, long long npix, int C0, int C1, int C2, void* grad_a, void* grad_b,
                            void* grad_tail, td_stream_t stream) {
   const int rc = join_check(grad_a, grad_b, grad_tail, grad_out, npix, C0, C1, C2);
   if (rc != TD_OK) return rc;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_join<__hip_bfloat16>(false, grad_a, grad_b, grad_tail, npix, C0, C1, C2, (void*)grad_out, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32) return td::run_join<float>(false, grad_a, grad_b, grad_tail, npix, C0, C1, C2, (void*)grad_out, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return td::run_join<T>("td_join_bwd", false, grad_a, grad_b, grad_tail, npix, C0, C1, C2, (void*)grad_out, (hipStream_t)stream);
+  });
 }
 
 static int join_up2_check(const void* a, const void* b, const void* t, const void* out, int N, int H, int W, int C0, int C1, int C2) {
@@ -177,20 +177,18 @@ extern "C" int td_join_up2_fwd(const void* a, const void* b_half, const void* ta
                                void* out, td_stream_t stream) {
   const int rc = join_up2_check(a, b_half, tail, out, N, H, W, C0, C1, C2);
   if (rc != TD_OK) return rc;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_join_up2<__hip_bfloat16>(true, (void*)a, (void*)b_half, (void*)tail, N, H, W, C0, C1, C2, out, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_join_up2<float>(true, (void*)a, (void*)b_half, (void*)tail, N, H, W, C0, C1, C2, out, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return td::run_join_up2<T>("td_join_up2_fwd", true, (void*)a, (void*)b_half, (void*)tail, N, H, W, C0, C1, C2, out, (hipStream_t)stream);
+  });
 }
 
 extern "C" int td_join_up2_bwd(const void* grad_out, int dtype, int N, int H, int W, int C0, int C1, int C2, void* grad_a,
                                void* grad_b_half, void* grad_tail, td_stream_t stream) {
   const int rc = join_up2_check(grad_a, grad_b_half, grad_tail, grad_out, N, H, W, C0, C1, C2);
   if (rc != TD_OK) return rc;
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_join_up2<__hip_bfloat16>(false, grad_a, grad_b_half, grad_tail, N, H, W, C0, C1, C2, (void*)grad_out, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_join_up2<float>(false, grad_a, grad_b_half, grad_tail, N, H, W, C0, C1, C2, (void*)grad_out, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::type;
+    return td::run_join_up2<T>("td_join_up2_bwd", false, grad_a, grad_b_half, grad_tail, N, H, W, C0, C1, C2, (void*)grad_out, (hipStream_t)stream);
+  });
 }

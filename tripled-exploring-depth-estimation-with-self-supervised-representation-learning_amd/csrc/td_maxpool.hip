@@ -432,43 +432,43 @@ extern "C" int td_maxpool5_fwd(const void* in, int dtype, int N, int H, int W, i
                                td_stream_t stream) {
   if (!in || !out || !idx || N <= 0 || H <= 0 || W <= 0 || C <= 0) return TD_ERR_BAD_ARG;
   if (C % 8 != 0) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16) return td::run_maxpool<__hip_bfloat16>(true, in, nullptr, N, H, W, C, out, idx, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32) return td::run_maxpool<float>(true, in, nullptr, N, H, W, C, out, idx, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    return td::run_maxpool<typename decltype(tag)::type>(true, in, nullptr, N, H, W, C, out, idx, (hipStream_t)stream);
+  });
 }
 
 extern "C" int td_maxpool5_bwd(const void* grad_out, const uint8_t* idx, int dtype, int N, int H, int W, int C,
                                void* grad_in, td_stream_t stream) {
   if (!grad_out || !idx || !grad_in || N <= 0 || H <= 0 || W <= 0 || C <= 0) return TD_ERR_BAD_ARG;
   if (C % 8 != 0) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16) return td::run_maxpool<__hip_bfloat16>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32) return td::run_maxpool<float>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    return td::run_maxpool<typename decltype(tag)::type>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream);
+  });
 }
 
 extern "C" int td_maxpool5_bwd_add(const void* grad_out, const uint8_t* idx, const void* add, int dtype, int N, int H, int W, int C,
                                    void* grad_in, td_stream_t stream) {
   if (!grad_out || !idx || !grad_in || N <= 0 || H <= 0 || W <= 0 || C <= 0) return TD_ERR_BAD_ARG;
   if (C % 8 != 0) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16) return td::run_maxpool<__hip_bfloat16>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream, add);
-  if (dtype == TD_DTYPE_F32) return td::run_maxpool<float>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream, add);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    return td::run_maxpool<typename decltype(tag)::type>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream, add);
+  });
 }
 
 extern "C" int td_maxpool3s2_fwd(const void* in, int dtype, int N, int H, int W, int C, void* out, uint8_t* idx,
                                  td_stream_t stream) {
   if (!in || !out || !idx || N <= 0 || H <= 0 || W <= 0 || C <= 0) return TD_ERR_BAD_ARG;
   if (C % 8 != 0) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16) return td::run_maxpool3s2<__hip_bfloat16>(true, in, nullptr, N, H, W, C, out, idx, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32) return td::run_maxpool3s2<float>(true, in, nullptr, N, H, W, C, out, idx, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    return td::run_maxpool3s2<typename decltype(tag)::type>(true, in, nullptr, N, H, W, C, out, idx, (hipStream_t)stream);
+  });
 }
 
 extern "C" int td_maxpool3s2_bwd(const void* grad_out, const uint8_t* idx, int dtype, int N, int H, int W, int C,
                                  void* grad_in, td_stream_t stream) {
   if (!grad_out || !idx || !grad_in || N <= 0 || H <= 0 || W <= 0 || C <= 0) return TD_ERR_BAD_ARG;
   if (C % 8 != 0) return TD_ERR_UNSUPPORTED;
-  if (dtype == TD_DTYPE_BF16) return td::run_maxpool3s2<__hip_bfloat16>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32) return td::run_maxpool3s2<float>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    return td::run_maxpool3s2<typename decltype(tag)::type>(false, grad_out, idx, N, H, W, C, grad_in, nullptr, (hipStream_t)stream);
+  });
 }

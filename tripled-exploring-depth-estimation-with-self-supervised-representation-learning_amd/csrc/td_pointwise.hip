@@ -111,11 +111,9 @@ extern "C" int td_l1map_fwd(const void* pred, int dtype, const long long* pred_s
   const int rc = l1map_check(pred, target, pred_strides, B, C, H, W);
   if (rc != TD_OK || !out) return rc != TD_OK ? rc : TD_ERR_BAD_ARG;
   const td::Strides4 sp{pred_strides[0], pred_strides[1], pred_strides[2], pred_strides[3]};
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_l1map<__hip_bfloat16>(true, pred, sp, target, B, C, H, W, weight, nullptr, out, nullptr, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_l1map<float>(true, pred, sp, target, B, C, H, W, weight, nullptr, out, nullptr, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    return td::run_l1map<typename decltype(tag)::type>(true, pred, sp, target, B, C, H, W, weight, nullptr, out, nullptr, (hipStream_t)stream);
+  });
 }
 
 extern "C" int td_l1map_bwd(const void* pred, int dtype, const long long* pred_strides, const float* target, const float* gmap,
@@ -123,11 +121,9 @@ extern "C" int td_l1map_bwd(const void* pred, int dtype, const long long* pred_s
   const int rc = l1map_check(pred, target, pred_strides, B, C, H, W);
   if (rc != TD_OK || !gmap || !dpred) return rc != TD_OK ? rc : TD_ERR_BAD_ARG;
   const td::Strides4 sp{pred_strides[0], pred_strides[1], pred_strides[2], pred_strides[3]};
-  if (dtype == TD_DTYPE_BF16)
-    return td::run_l1map<__hip_bfloat16>(false, pred, sp, target, B, C, H, W, weight, gmap, nullptr, dpred, (hipStream_t)stream);
-  if (dtype == TD_DTYPE_F32)
-    return td::run_l1map<float>(false, pred, sp, target, B, C, H, W, weight, gmap, nullptr, dpred, (hipStream_t)stream);
-  return TD_ERR_UNSUPPORTED;
+  return td::dispatch_dtype(dtype, [&](auto tag) {
+    return td::run_l1map<typename decltype(tag)::type>(false, pred, sp, target, B, C, H, W, weight, gmap, nullptr, dpred, (hipStream_t)stream);
+  });
 }
 
 extern "C" int td_rgb2lab(const float* rgb, int B, int H, int W, float l_cent, float l_norm, float ab_norm, float* lab,

@@ -134,7 +134,8 @@ def check(code, what):
     if code != 0:
         lib = load()
         msg = lib.td_error_string(code).decode()
-        hip = lib.td_last_hip_error().decode()
+        # the record holds the last failed LAUNCH of this thread, whichever call that was: it explains TD_ERR_LAUNCH and nothing else
+        hip = lib.td_last_hip_error().decode() if code == CONSTANTS["TD_ERR_LAUNCH"] else ""
         raise NativeLibraryError("%s failed: %s (%d)%s" % (what, msg, code, (" [" + hip + "]") if hip else ""))
 
 
