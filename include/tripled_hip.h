@@ -871,6 +871,44 @@ int td_tsdf_surface(const long long* keys, const long long* sums, long long V, d
                     float* normal, uint8_t* rgb, int* weight, uint8_t* mask, long long* stats, td_stream_t stream);
 
 /*
+ * The TSDF map ray-cast into camera views: depth, camera-space normal, colour and weight per pixel (csrc/td_tsdf_cast.hip,
+ * tripled_amd/tsdf.py).  The reference has no such program: the statement is tsdf.raycast_numpy, which the kernel equals bit for bit.
+ *
+ * td_tsdf_cast: one fill (the stats rows) and one launch whatever C is, one thread per pixel, no synchronisation, no allocation.
+ *   keys [V] int64 ascending and unique, sums [V,7] int64: td_tsdf_surface's rows;  poses [C,3,4] float64 camera-to-world (device);
+ *   inv_K [9] float64 (device), as td_tsdf_samples': no TD_HOST parameter;  inv_voxel = 1 / voxel, computed once by the caller.
+ *   A voxel qualifies when w >= min_weight;  D = (double)S / (double)w  (td_tsdf_surface).  Per camera [R|t] and pixel (x, y), float64,
+ *   every operation rounded on its own (ray, camera_to_world: td_tsdf_samples'):
+ *     step = step_voxels voxel;  n_steps = floor((z_far - z_near) / step) + 1
+ *     for s = 0 ... n_steps-1:  z_s = z_near + (double)s step;  f = z_s / ray_z;  world = camera_to_world(ray f);  g = world inv_voxel
+ *       corners(g):  h_k = g_k - 0.5;  i_k = floor(h_k);  f_k = h_k - i_k;  known when every i_k lies in [-2^20, 2^20 - 1) (a NaN fails;
+ *         the last coordinate of a key field has no + neighbour, nothing is carried into the next field) and the eight voxels
+ *         i + {0,1}^3 are in keys, qualify and are not the sentinel voxel (the +z corner of a column is the next row)
+ *       v: along z  c_xy = D_xy0 + f_z (D_xy1 - D_xy0);  along y  c_x = c_x0 + f_y (c_x1 - c_x0);  along x  v = c_0 + f_x (c_1 - c_0)
+ *       prev = sample s-1 if it was known.   hit: prev known, v_prev >= 0, v < 0:  t = v_prev / (v_prev - v);  z_hit = z_(s-1) + t step
+ *       back face: prev known, v_prev < 0, v >= 0: the ray ends without a hit.   A ray that runs out of samples is a miss.
+ *     at a hit:  g_hit from z_hit as g from z_s, its corners fetched again;  with e the differences of D along the gradient's axis
+ *       G_0: e_yz along z, then y;  G_1: e_xz along z, then x;  G_2: e_xy along y, then x;  n = G / sqrt((G_0 G_0 + G_1 G_1) + G_2 G_2)
+ *       normal_k = (float)((R_0k n_0 + R_1k n_1) + R_2k n_2): it faces where the surface was seen from and is NOT turned to the viewer;
+ *       (0, 0, 0), and counted, when the corners of g_hit are not all known or the root is not > 0
+ *       colour (2 sum_c + w) / (2 w) and weight w (saturating at int32) of the voxel floor(g_hit): the corner c_k = (floor(g_k) != i_k);
+ *       when the corners of g_hit are not all known, of sample s by the same rule on g_s
+ *   depth [C,H,W] float32 (out): (float)z_hit, 0 without a hit;  normal [C,3,H,W] float32 (out);  color [C,3,H,W] uint8 (out): the
+ *   background without a hit;  weight [C,H,W] int32 (out): 0 without a hit;  every element is written.
+ *   stats [C,TD_TSDF_CAST_STATS] int64 (out, zeroed by the call): rays, hits, back faces, misses (rays = hits + back faces + misses), hits
+ *   whose normal is (0, 0, 0).  LDS counters per workgroup, then at most five integer atomics: no floating-point atomics, no kernel
+ *   waits on another workgroup, two calls on the same inputs return the same bits.
+ *   TD_ERR_BAD_ARG before any launch: a null pointer (also with V = 0), V < 0, C < 0, H or W < 1, voxel or inv_voxel not positive and finite, min_weight < 1, z_near not > 0, z_far not finite or below
+ *   z_near, step_voxels not positive and finite, pose_scale not finite, a background outside 0 ... 255.  TD_ERR_UNSUPPORTED: n_steps >
+ *   TD_TSDF_CAST_MAX_STEPS, C > 65535, H W > 2^31 - 1.  C = 0 is a successful no-op without a launch;  V = 0 is legal: every ray is a miss.
+ */
+#define TD_TSDF_CAST_MAX_STEPS 65536 /* the most samples per ray: a guard against a runaway launch, not a tuning value */
+#define TD_TSDF_CAST_STATS 5
+int td_tsdf_cast(const long long* keys, const long long* sums, long long V, const double* poses, const double* inv_K, int C, int H, int W, double voxel, double inv_voxel,
+                 long long min_weight, double z_near, double z_far, double step_voxels, double pose_scale, int bg_r, int bg_g, int bg_b,
+                 float* depth, float* normal, uint8_t* color, int* weight, long long* stats, td_stream_t stream);
+
+/*
  * KITTI ground-truth depth maps from velodyne scans, a batch of frames of different sizes per call (csrc/td_velo.hip,
  * tripled_amd/velodyne.py).  Replaces generate_depth_map, mono/datasets/kitti_utils.py:50-102 (the projection :71-86, the last-write
  * scatter :89-90, the duplicate rule with sub2ind :43-47,93-99, the clamp :100), which KITTIRAWDataset.get_depth calls per frame,

@@ -5,7 +5,8 @@ voxel-averaged coloured point cloud (binary PLY: x y z float, red green blue uch
   python scripts/reconstruct.py --config config/cfg_kitti_tripleD.py --checkpoint work/epoch_20.pth --data_path /data/kitti_odom \
          --sequence 9 [--frames A:B] [--poses FILE] [--voxel V] [--stride S] [--border P] [--max_range R] [--edge E] [--min_count N] \
          [--min_views M] [--view_radius R] [--view_tol T] [--depth_scale S] [--pose_scale S] [--batch_size 12] [--precision bf16] \
-         [--post_process] [--device cpu] [--save_poses FILE] [--tsdf [--trunc_voxels 3] [--min_weight 2]] --out cloud.ply
+         [--post_process] [--device cpu] [--save_poses FILE] [--tsdf [--trunc_voxels 3] [--min_weight 2] [--save_map map.npz]] \
+         --out cloud.ply
 
 Frames: <data_path>/sequences/NN/image_0/%06d.png; the frame count is the line count of <data_path>/poses/NN.txt (or of --poses).
 Without --poses the model's own poses are used (depth and pose share the model's scale); --poses FILE takes camera-to-world poses
@@ -22,7 +23,9 @@ pixel adds its signed distance to the voxels its ray meets within --trunc_voxels
 per voxel edge on which the averaged distance changes sign, between voxels of at least --min_weight samples (both untuned starting
 values), with nx ny nz after count: unit normals that face where the surface was seen from, so render_cloud.py --surfels and
 eval_cloud.py use them as they are.  count holds the edge's weight.  --min_count does not apply; --min_views composes through the
-per-pixel mask.  Without --tsdf nothing of this runs and the output is what it always was.
+per-pixel mask.  Without --tsdf nothing of this runs and the output is what it always was.  --save_map FILE (with --tsdf) also writes
+the fused voxel map itself (tripled_amd.tsdf.save_map: one .npz of keys, integer rows, voxel and band), which
+scripts/render_cloud.py --map ray-casts into depth, normal and colour images.
 """
 import argparse
 import os
@@ -70,8 +73,11 @@ def main():
     ap.add_argument("--tsdf", action="store_true", help="fuse truncated signed distances: surface points with oriented normals")
     ap.add_argument("--trunc_voxels", type=int, default=tsdf.DEFAULT_TRUNC_VOXELS, help="the band on either side of a surface, in voxels (untuned)")
     ap.add_argument("--min_weight", type=int, default=tsdf.DEFAULT_MIN_WEIGHT, help="samples a voxel needs to take part in the surface (untuned)")
+    ap.add_argument("--save_map", default=None, help="with --tsdf: write the fused voxel map (.npz) for render_cloud.py --map")
     ap.add_argument("--out", required=True)
     args = ap.parse_args()
+    if args.save_map and not args.tsdf:
+        ap.error("--save_map writes the map of --tsdf")
     cfg = Config.fromfile(args.config)
     cfg.model["imgs_per_gpu"] = 1
     height, width = args.height or cfg.model["height"], args.width or cfg.model["width"]
@@ -108,6 +114,10 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.save_poses)), exist_ok=True)
         odometry.save_kitti_poses(args.save_poses, fuser.poses)
         print("saved %d poses to %s" % (len(fuser.poses), args.save_poses))
+    if args.save_map:
+        os.makedirs(os.path.dirname(os.path.abspath(args.save_map)), exist_ok=True)
+        tsdf.save_map(args.save_map, *fuser.map, args.voxel, args.trunc_voxels)
+        print("saved %d voxels to %s" % (len(fuser.map[0]), args.save_map))
     print(" ".join("%s %d" % (k, v) for k, v in result.stats.items()))
     if args.min_views and not args.tsdf:
         kept, tested = result.stats["valid"], result.stats["valid"] + result.stats["invalid_views"]

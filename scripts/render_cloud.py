@@ -6,6 +6,9 @@ and no checkpoint are needed.  The reference has no such program.
          (--config config/cfg_kitti_tripleD.py | --K fx fy cx cy) [--height H --width W] [--near Z] [--far Z] [--splat S] \
          [--pose_scale S] [--top] [--save_depth] [--device cpu] --out DIR \
          [--surfels [--surfel_radius R] [--cull] [--ambient A] [--save_normals]]
+  python scripts/render_cloud.py --map map.npz --poses poses.txt [--frames A:B] [--every N] (--config ... | --K fx fy cx cy) \
+         [--height H --width W] [--near Z] [--far Z] [--step_voxels S] [--min_weight N] [--pose_scale S] [--save_depth] \
+         [--save_normals] [--device cpu] --out DIR
 
 --poses: camera-to-world poses in KITTI pose text (reconstruct.py --save_poses writes the ones a cloud was fused with; with the
 ground truth give the --pose_scale the cloud was fused with).  --frames A:B takes the poses A ... B-1, --every N every N-th of them.
@@ -29,6 +32,13 @@ camera-space normal, turned towards the viewer, from [-1, 1] to [0, 255]; black 
 view_%06d_normal.npy (float32 [3,H,W]).  --top works the same way through the orthographic camera.  Limits: one radius for all
 discs, the nearest disc wins a pixel (no blending), a disc's pixel box is capped at 33 x 33 (counted as capped), and the nearest camera
 is only a guess at the side a surface was seen from.
+--map (instead of --cloud) takes the TSDF map that reconstruct.py --tsdf --save_map wrote and ray-casts it
+(tripled_amd.tsdf.TsdfCaster, csrc/td_tsdf_cast.hip on a HIP device): every pixel's ray is walked through the signed-distance field in
+steps of --step_voxels voxels of the camera's z to the first front-facing zero crossing; there is no radius to pick, and no holes where
+the field is known.  Voxels of fewer than --min_weight samples do not take part.  The same view_%06d_color.png, _depth.png, _normal.png
+(the normal faces where the surface was SEEN from; it is not turned towards the viewer) and .npy files are written; the five counters
+(rays, hits, backface, misses, hits_without_normal) are printed per view and in total.  --step_voxels, --min_weight, --near and --far
+are untuned starting values.  --top is not available with --map (the cast is perspective only).
 """
 import argparse
 import os
@@ -41,7 +51,7 @@ from PIL import Image
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import tripled_amd  # noqa: F401,E402
-from tripled_amd import cloud, cloud_eval, cloud_normals, infer, odometry, render  # noqa: E402
+from tripled_amd import cloud, cloud_eval, cloud_normals, infer, odometry, render, tsdf  # noqa: E402
 
 
 def depth_picture(depth):
@@ -103,9 +113,38 @@ def stats_line(name, stats, pixels):
     return "%s %s share_hit %.4f" % (name, " ".join("%s %d" % (k, v) for k, v in zip(render.STATS, stats)), stats[4] / pixels)
 
 
+def cast_stats_line(name, stats):
+    return "%s %s share_hit %.4f" % (name, " ".join("%s %d" % (k, v) for k, v in zip(tsdf.CAST_STATS, stats)), stats[1] / max(stats[0], 1))
+
+
+def cast_map(args, poses, numbers, height, width, K):
+    """--map: the views of the poses ``numbers``, ray-cast from the TSDF map."""
+    keys, sums, voxel, _ = tsdf.load_map(args.map)
+    caster = tsdf.TsdfCaster(args.device, height, width, K, voxel, min_weight=args.min_weight, near=args.near, far=args.far,
+                             step_voxels=args.step_voxels, pose_scale=args.pose_scale, batch_size=args.batch_size)
+    print("-> Casting %d voxels of %g into %d views of %d x %d" % (len(keys), voxel, len(numbers), height, width))
+    if caster.on_hip:                                             # once; a batch of views at a time is held on the host
+        keys, sums = torch.from_numpy(keys).to(caster.device), torch.from_numpy(sums).to(caster.device)
+    total = np.zeros(len(tsdf.CAST_STATS), np.int64)
+    for at in range(0, len(numbers), args.batch_size):
+        batch = numbers[at:at + args.batch_size]
+        out = caster.cast(keys, sums, poses[batch])
+        for j, n in enumerate(batch):
+            save_view(args.out, "view_%06d" % n, out.depth[j], out.color[j], args.save_depth)
+            Image.fromarray(normal_picture(out.normal[j], out.weight[j] - 1)).save(os.path.join(args.out, "view_%06d_normal.png" % n))
+            if args.save_normals:
+                np.save(os.path.join(args.out, "view_%06d_normal.npy" % n), out.normal[j])
+            print(cast_stats_line("view %06d" % n, out.stats[j]))
+            total += out.stats[j]
+    print(cast_stats_line("total over %d views" % len(numbers), total))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--cloud", required=True, help="the PLY of scripts/reconstruct.py")
+    ap.add_argument("--cloud", default=None, help="the PLY of scripts/reconstruct.py")
+    ap.add_argument("--map", default=None, help="instead of --cloud: the TSDF map of scripts/reconstruct.py --tsdf --save_map, ray-cast")
+    ap.add_argument("--step_voxels", type=float, default=tsdf.DEFAULT_STEP_VOXELS, help="--map: the step along the camera's z in voxels (untuned)")
+    ap.add_argument("--min_weight", type=int, default=tsdf.DEFAULT_MIN_WEIGHT, help="--map: voxels of fewer samples do not take part (untuned)")
     ap.add_argument("--poses", required=True, help="camera-to-world poses in KITTI pose text")
     ap.add_argument("--frames", default=None, help="A:B, the poses A ... B-1 (default: all)")
     ap.add_argument("--every", type=int, default=1)
@@ -132,6 +171,12 @@ def main():
     ap.add_argument("--min_neighbours", type=int, default=6, help="fewer neighbours: no normal (untuned)")
     ap.add_argument("--max_curvature", type=float, default=0.01, help="a rougher patch (lambda_min / trace): no normal (untuned)")
     args = ap.parse_args()
+    if (args.cloud is None) == (args.map is None):
+        ap.error("one of --cloud and --map")
+    if args.map and args.top:
+        ap.error("--top draws a cloud through an orthographic camera; the ray cast of --map is perspective only")
+    if args.map and args.surfels:
+        ap.error("--surfels draws a cloud; --map needs no discs")
     if (args.config is None) == (args.K is None):
         ap.error("one of --config and --K")
     if args.every < 1:
@@ -151,15 +196,17 @@ def main():
         height, width = args.height, args.width
         fx, fy, cx, cy = args.K
         K = np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]])
-    points = cloud.load_ply(args.cloud)
-    xyz = np.stack([points["x"], points["y"], points["z"]], 1).astype(np.float32)
-    rgb = np.stack([points["red"], points["green"], points["blue"]], 1).astype(np.uint8)
     poses = odometry.load_kitti_poses(args.poses)
     a, _, b = (args.frames or ":").partition(":")
     numbers = list(range(int(a or 0), min(int(b or len(poses)), len(poses)), args.every))
     if not numbers:
         ap.error("--frames %s of %d poses: nothing to draw" % (args.frames, len(poses)))
     os.makedirs(args.out, exist_ok=True)
+    if args.map:
+        return cast_map(args, poses, numbers, height, width, K)
+    points = cloud.load_ply(args.cloud)
+    xyz = np.stack([points["x"], points["y"], points["z"]], 1).astype(np.float32)
+    rgb = np.stack([points["red"], points["green"], points["blue"]], 1).astype(np.uint8)
     renderer = render.CloudRenderer(args.device, height, width, K, near=args.near, far=args.far, splat=args.splat,
                                     pose_scale=args.pose_scale, batch_size=args.batch_size)
     print("-> Drawing %d points into %d views of %d x %d" % (len(xyz), len(numbers), height, width))

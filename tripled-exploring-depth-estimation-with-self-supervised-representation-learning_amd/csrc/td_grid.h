@@ -1,4 +1,4 @@
-// What the cloud kernels share (td_cloud, td_tsdf, td_scan, td_views, td_nn, td_normals): the voxel / cell key, the pieces of the walk over a grid of
+// What the cloud kernels share (td_cloud, td_tsdf, td_tsdf_cast, td_scan, td_views, td_nn, td_normals): the voxel / cell key, the pieces of the walk over a grid of
 // cells sorted by it, and the camera-to-world transform.  Every user is built with -ffp-contract=off: each float64 product and sum below is
 // rounded on its own, as the numpy statements (cloud.grid_keys_numpy, cloud_eval.walk_numpy) round it.
 #pragma once
@@ -45,6 +45,12 @@ __device__ __forceinline__ void camera_to_world(const double* __restrict__ P, do
   wx = ((P[0] * x + P[1] * y) + P[2] * z) + scale * P[3];
   wy = ((P[4] * x + P[5] * y) + P[6] * z) + scale * P[7];
   wz = ((P[8] * x + P[9] * y) + P[10] * z) + scale * P[11];
+}
+
+// A row of the TSDF map (td_tsdf, td_tsdf_cast): S = sum q - 2^20 w, the summed signed distance, an exact integer
+#define TD_TSDF_ONE 1048576      // 2^20: the distance `trunc` as an integer
+__device__ __forceinline__ long long tsdf_sum(const long long* __restrict__ r) {
+  return (r[1] + 1024 * r[2] + (long long)TD_TSDF_ONE * r[3]) - (long long)TD_TSDF_ONE * r[0];
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

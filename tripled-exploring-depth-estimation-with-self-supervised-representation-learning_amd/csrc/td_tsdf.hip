@@ -12,8 +12,6 @@
 #include "td_grid.h"
 #include "td_pixel.h"
 
-#define TD_TSDF_ONE 1048576      // 2^20: the distance `trunc` as an integer
-
 namespace td {
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -119,11 +117,6 @@ __global__ __launch_bounds__(TD_THREADS) void tsdf_samples_kernel(const TsdfSamp
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // surface
-
-// S = sum q - 2^20 w: the summed signed distance of a row, an exact integer
-__device__ __forceinline__ long long tsdf_sum(const long long* __restrict__ r) {
-  return (r[1] + 1024 * r[2] + (long long)TD_TSDF_ONE * r[3]) - (long long)TD_TSDF_ONE * r[0];
-}
 
 // The index of the neighbour of voxel `idx` (key `key`) one step along `axis` (0 x, 1 y, 2 z) in direction dir = +-1, or -1.  The
 // coordinate field is tested first: the last coordinate has no + neighbour and the first no - neighbour, and nothing is ever carried
